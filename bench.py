@@ -1,11 +1,23 @@
 """slam355 benchmark — the driver contract.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload tracking|ba|matcher]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload tracking|ba|matcher|vo]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W untimed and K timed steps of the workload, and
+prints the result line: `value` and `ms_per_step` come from those K steps alone.
+`--dump-outputs DIR` then also writes what the last timed step computed (the
+arrays a caller of the timed path receives) as DIR/<name>.npy, float32 or
+float64, at most 64 MB in all; the inputs are seeded, so two builds run with
+the same arguments can be compared array for array.  `--full` adds every
+measurement that takes runs of its own and is reported beside the headline:
+the PCIe-inclusive and tracked-source regions, the local BA of a tracked
+window, the sharded C4 window, the CPU baselines and C5's pose-graph solve
+(each still has its own --no-... switch).
 
 Default workload ("tracking", BASELINE.json metric "frames/sec tracking+local-BA
 @1280x720"): one step = B synthetic 1280x720 stereo frame pairs, resident in
-HBM before the timed region (the PCIe-inclusive rate, frames streamed from
-pinned host memory, is reported beside it), through the whole tracking hot
+HBM before the timed region (with --full the PCIe-inclusive rate, frames streamed
+from pinned host memory, is reported beside it), through the whole tracking hot
 path (ORB on 2B+1 images with 64 kp/tile ~ 2075 kp/frame, on its own CU-masked
 stream pipelined against the previous batch's tail; stereo kNN-2 + ratio,
 F-LMedS, triangulation, temporal kNN-2 + gate, PnP-RANSAC, device pose chain)
@@ -141,6 +153,41 @@ def timed_loop(step, steps, warmup, world, marks_every=True, dict_marks=False):
             for (n0, e0), (n1, e1) in zip(lane[:-1], lane[1:]):
                 stages.setdefault(n1, []).append(e0.elapsed_time(e1))
     return reduce_scalar(dt, world, "max"), {k: float(np.mean(v)) for k, v in stages.items()}
+
+
+DUMP_BUDGET = 64 * 1000 * 1000  # bytes --dump-outputs may write in all
+
+
+def valid_rows(a, cnt):
+    """Host copy of a [N, cap, ...] device buffer with the rows past cnt[n] zeroed
+    (they hold leftovers of earlier batches, not outputs of this step)."""
+    a, cnt = a.cpu().numpy().copy(), cnt.cpu().numpy()
+    a[np.arange(a.shape[1])[None, :] >= cnt[:, None]] = 0
+    return a
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: {name: array or tensor} -> DIR/<name>.npy, float32 and 8/16-bit
+    integers as float32, everything else as float64.  Smallest first, an array
+    over an equal share of what is left of DUMP_BUDGET is written as a fixed
+    sample: the flat elements at the sorted indices of default_rng(0).choice(size,
+    n, replace=False), the same in every run.  Returns {name: shape written}."""
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        f32 = a.dtype == np.float32 or (a.dtype.kind in "bui" and a.itemsize <= 2)  # exact in f32
+        host[name] = np.ascontiguousarray(a, dtype=np.float32 if f32 else np.float64)
+    left, shapes = DUMP_BUDGET - 256 * len(host), {}  # 128-byte .npy headers, with room
+    for i, name in enumerate(sorted(host, key=lambda k: host[k].nbytes)):
+        a, share = host[name], left // (len(host) - i)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.ravel()[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        left -= a.nbytes
+        shapes[name] = list(a.shape)
+    return shapes
 
 
 def ba_flops_per_iter(C, P, O, n_per_pt):
@@ -312,7 +359,8 @@ def run_tracking(args, world, rank):
     feed_h2d = None if args.no_pcie_leg else FrameFeed(L, R, B, n_win, resident=False)
     feeds = [feed]
     CPU_PAIRS = 16  # cpu_baseline sample: 16 frame pairs + 16 LM iterations (~10 s of host work)
-    L_np, R_np = L[:CPU_PAIRS + 1].cpu().numpy(), R[:CPU_PAIRS].cpu().numpy()
+    if not args.no_cpu_baseline:
+        L_np, R_np = L[:CPU_PAIRS + 1].cpu().numpy(), R[:CPU_PAIRS].cpu().numpy()
     del L, R
     # the global trajectory of the shards (world > 1): one all-gather of the
     # step's PnP results + the device pose chain over all world * B pairs, every
@@ -553,6 +601,26 @@ def run_tracking(args, world, rank):
     # slowest single call (a call that blocks on the device shows up as a max)
     host_sites = host_site_summary(trk, args.steps)
     main_step_s, main_host_s = timed_loop.step_s, timed_loop.host_s
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left: the tracked batch (Tracker.track's results,
+        # its chained poses and the stage outputs behind them, rows past each count
+        # zeroed) and the windows of the last local-BA launch set
+        nkp, wins = trk.ows.count, [p for bt in bas for p in bt.problems]
+        par = [p.params() for p in wins]
+        dumped = dump_outputs(args.dump_outputs, {
+            "poses": trk.poses if gchain is None else gchain.poses,
+            "rvec": trk.rvec, "tvec": trk.tvec, "pnp_inliers": trk.p_ninl,
+            "pnp_mask": valid_rows(trk.p_mask, trk.t_cnt),
+            "orb_count": nkp, "orb_keypoints": valid_rows(trk.ows.kp, nkp),
+            "orb_octave": valid_rows(trk.ows.octave, nkp),
+            "orb_descriptors": valid_rows(trk.ows.desc, nkp),
+            "stereo_count": trk.s_cnt, "f_inlier_count": trk.f_cnt, "fundamental": trk.f_F,
+            "points3d": valid_rows(trk.X, trk.f_cnt), "temporal_count": trk.t_cnt,
+            "pnp_object_points": valid_rows(trk.Q1, trk.t_cnt),
+            "pnp_image_points": valid_rows(trk.q2, trk.t_cnt),
+            "ba_cams": np.stack([c for c, _ in par]), "ba_points": np.stack([p for _, p in par]),
+            "ba_cost": np.array([p.state()["COST"] for p in wins])})
     pcie = None
     if feed_h2d is not None:
         # the same steps with the frames uploaded from pinned host memory inside
@@ -736,6 +804,8 @@ def run_tracking(args, world, rank):
                      # sizes with equal world * batch (the same pairs per global step)
                      "trajectory_sha1": hashlib.sha1(np.ascontiguousarray(est).tobytes()).hexdigest()},
     }
+    if dumped is not None:
+        rec["dumped_outputs"] = dumped
     if pcie is not None:
         rec["pcie_inclusive"] = pcie
     if tracked is not None:
@@ -944,12 +1014,17 @@ def run_ba(args, world, rank):
         else:  # one LM iteration = one HIP-graph replay (3T + 5 launches for the tiled solver)
             step_fn = lambda: prob.iterate_graphed(1)  # noqa: E731
 
-    pose_graph = pose_graph_solve(C) if name == "C5" and rank == 0 else None
+    pose_graph = pose_graph_solve(C) if name == "C5" and rank == 0 and args.full else None
 
     def step(marks):
         step_fn()
 
     dt, _ = timed_loop(step, args.steps, args.warmup, world, marks_every=False)
+    dumped = None
+    if args.dump_outputs and rank == 0:  # this rank's parameters after the K-th iteration
+        cams, pts = prob.params()
+        dumped = dump_outputs(args.dump_outputs, {"ba_cams": cams, "ba_points": pts,
+                                                  "ba_cost": np.array([prob.state()["COST"]])})
     flops = ba_flops_per_iter(C, P, P * k, k)
     if packed(C):  # tiled solver: count the tile envelope it factors, not a dense (9C)^3/3
         flops += tiled_solve_flops(C, prob.plan["blocks"]) - (9 * C) ** 3 / 3
@@ -969,7 +1044,7 @@ def run_ba(args, world, rank):
                      "unit": "TFLOP/s", "frac": achieved / F64_PEAK_TFLOPS, "traffic": None,
                      "kernel": "LM iteration", "flops_per_iter": flops},
         "final_cost": prob.state()["COST"],
-    } | ({"pose_graph": pose_graph,
+    } | ({"dumped_outputs": dumped} if dumped is not None else {}) | ({"pose_graph": pose_graph,
           "c5_pose_graph_plus_ba_ms": pose_graph["ms_per_solve"] + args.ba_iters * dt / args.steps * 1e3,
           "c5_sequence": f"pose-graph TRF solve to convergence, then {args.ba_iters} full-BA LM "
                          "iterations (BundleAdjustment.py:179-182, then :397-402)"}
@@ -1043,10 +1118,16 @@ def run_ba_batch(args, world, rank):
             cur.wait_stream(st)
 
     dt, _ = timed_loop(step, args.steps, args.warmup, world, marks_every=False)
+    dumped = None
+    if args.dump_outputs and rank == 0:  # every window's parameters after the K-th iteration
+        par = [p.params() for p in probs]
+        dumped = dump_outputs(args.dump_outputs, {
+            "ba_cams": np.stack([c for c, _ in par]), "ba_points": np.stack([p for _, p in par]),
+            "ba_cost": np.array([p.state()["COST"] for p in probs])})
     flops = args.ba_batch * ba_flops_per_iter(C, P, P * k, k)
     it_s = args.steps / dt
     achieved = flops * it_s / 1e12
-    return {
+    return ({"dumped_outputs": dumped} if dumped is not None else {}) | {
         "metric": "local-BA LM iterations/sec (batched C3 windows)",
         "value": reduce_scalar(args.ba_batch * it_s, world, "sum"), "unit": "window-iters/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1096,7 +1177,11 @@ def run_matcher(args, world, rank):
     roof = matcher_roofline(pairs, kms, t.shape[1], f"batch {args.batch}", args.valu)
     roof["frac"] = roof["achieved"] / roof["peak"]
     roof["traffic"] = None
-    return {
+    dumped = None
+    if args.dump_outputs and rank == 0:  # knn2_batch's (idx2, dist2, good), rows past each nq zeroed
+        dumped = dump_outputs(args.dump_outputs, {
+            n: valid_rows(o, tnq) for n, o in zip(("knn2_index", "knn2_distance", "ratio_good"), out)})
+    return ({"dumped_outputs": dumped} if dumped is not None else {}) | {
         "metric": "BF-Hamming kNN-2 match throughput @ C2 (2000x2000 x 32 B descriptors)",
         "value": reduce_scalar(pairs * args.steps, world, "sum") / dt / 1e9, "unit": "Gpairs/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1197,6 +1282,10 @@ def run_vo(args, world, rank):
                "with_disparity_mean": float(out["cnt"].float().mean()),
                "t_err_max": float(np.abs(dof[:, 5] - np.array(gt_dz)).max())},
     }
+    if args.dump_outputs and rank == 0:  # the last step's poses and the counts behind them
+        rec["dumped_outputs"] = dump_outputs(args.dump_outputs, {
+            "pose": out["pose"], "fast_count": out["nkp"], "tracked_count": out["ntp"],
+            "with_disparity_count": out["cnt"]})
     if rank == 0 and not args.no_cpu_baseline:
         rec["cpu_baseline"] = cpu_baseline_vo(L, R, rig)
     return rec
@@ -1278,9 +1367,18 @@ def main():
                     help="which stream gets the high HIP stream priority (tracking workload)")
     ap.add_argument("--ba-serial", action="store_true",
                     help="run local BA on the tracking stream (no overlap)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all; seeded inputs, so two builds "
+                         "compare array for array; tracking: always of the synthetic-window "
+                         "region, which --ba-source tracked runs first too)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what is reported beside the headline in runs of its own: "
+                         "PCIe-inclusive and tracked-source regions, tracked-window BA, sharded C4 "
+                         "window, CPU baselines, C5's pose-graph solve (default: the timed steps only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-ba-scale", action="store_true",
-                    help="tracking: skip the sharded C4 local-BA iterations/s measurement")
+                    help="tracking --full: skip the sharded C4 local-BA iterations/s measurement")
     ap.add_argument("--track-cus", type=int, default=0,
                     help="restrict the tracking stream to this many CUs (0: all); the rest run "
                          "only local-BA work, whose latency-bound kernels then do not share "
@@ -1321,6 +1419,9 @@ def main():
     args = ap.parse_args()
     if args.tracked_lag < 1:
         ap.error("--tracked-lag must be >= 1 (0 would stage the window mapper the same step fills)")
+    if not args.full:  # a plain run times the headline only; --ba-source tracked takes it from that leg
+        args.no_cpu_baseline = args.no_ba_scale = args.no_pcie_leg = args.no_tracked_ba = True
+        args.no_tracked_leg = args.no_tracked_leg or args.ba_source != "tracked"
     if args.batch is None:
         args.batch = 64 if args.workload == "tracking" else 32
     if args.windows is None:  # global steps in the sequence (each world * batch pairs)
@@ -1337,6 +1438,7 @@ def main():
     run = {"tracking": run_tracking, "ba": run_ba, "matcher": run_matcher,
            "vo": run_vo}[args.workload]
     rec = run(args, world, rank)
+    rec["full"] = args.full
     if rank == 0:
         print(json.dumps(rec), flush=True)
     if world > 1:

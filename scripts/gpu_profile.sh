@@ -9,7 +9,7 @@ shift || true
 OUT="$ROOT/gpurun_out/prof_$TAG"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-B="$ROOT/bench.py --no-cpu-baseline --no-ba-scale $*"
+B="$ROOT/bench.py --full --no-cpu-baseline --no-ba-scale $*"
 timeout -k 10 240 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run \
   -- python3 $B --steps 20 --warmup 5 > "$OUT/stats.log" 2>&1 || exit 1
 for c in FETCH_SIZE WRITE_SIZE; do

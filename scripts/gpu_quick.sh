@@ -11,5 +11,5 @@ if [ -n "$K" ]; then
   timeout -k 10 500 python -u -m pytest tests -x -v -m gpu -k "$K" --timeout 200 --timeout-method thread > "$OUT/pytest.log" 2>&1 || { tail -40 "$OUT/pytest.log"; exit 1; }
   tail -2 "$OUT/pytest.log"
 fi
-timeout -k 10 240 python3 bench.py --gpus 1 --steps 20 --warmup 5 "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
+timeout -k 10 240 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
 python3 -c "import json;d=json.load(open('$OUT/bench.json'));print(round(d['value']),round(d['ms_per_step'],3),round(d['host_issue_ms_per_step'],3), d.get('pcie_inclusive',{}).get('frames_per_s'))"

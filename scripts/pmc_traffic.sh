@@ -13,6 +13,6 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d "$OUT/$c" -o run \
-    -- python3 "$ROOT/bench.py" --steps 3 --warmup 1 --no-cpu-baseline "$@" > "$OUT/$c.log" 2>&1 || exit $?
+    -- python3 "$ROOT/bench.py" --steps 3 --warmup 1 --full --no-cpu-baseline "$@" > "$OUT/$c.log" 2>&1 || exit $?
 done
 python3 "$ROOT/scripts/pmc_summary.py" "$OUT" "$ROOT/gpurun_out/pmc_traffic_${TAG}.json"
