@@ -121,6 +121,21 @@ int slam_gather_temporal(const double* d_X, const double* d_ptl, int xcap, const
 int slam_fundamental_lmeds(const double* d_m1, const double* d_m2, const int32_t* d_count,
                            int cap, int batch, uint64_t seed, int item0, int n_hyp,
                            uint8_t* d_mask, double* d_F, int32_t* d_ninliers, void* stream);
+/* slam_fundamental_lmeds on a caller-owned workspace d_ws of ws_len doubles (the
+ * hypotheses' candidate matrices, written by one kernel and scored by the
+ * next): the form for a hot loop.  Same results bit for bit.  A ws_len below
+ * slam_fundamental_workspace_len(batch, n_hyp) returns SLAM_ERR_ARG with a
+ * message naming the needed length, before any GPU call.  The workspace is the
+ * caller's: calls that may overlap (other streams) need their own; it need not
+ * be cleared between calls.  slam_fundamental_lmeds itself takes its workspace
+ * from the stream's memory pool (hipMallocAsync / hipFreeAsync on `stream`). */
+int slam_fundamental_lmeds_ws(const double* d_m1, const double* d_m2, const int32_t* d_count,
+                              int cap, int batch, uint64_t seed, int item0, int n_hyp,
+                              uint8_t* d_mask, double* d_F, int32_t* d_ninliers, double* d_ws,
+                              long long ws_len, void* stream);
+/* Doubles of slam_fundamental_lmeds_ws's workspace (28 per pair and hypothesis);
+ * monotone in both arguments, 0 when either is <= 0. */
+long long slam_fundamental_workspace_len(int batch, int n_hyp);
 
 /* Order-preserving compaction of pairs[b][k] (k < count[b]) where mask[b][k] != 0
  * (the `pts_left[mask]` of keypoint.py:63-66). d_out must not alias d_pairs. */

@@ -57,6 +57,12 @@ int main(void) {
   /* epipolar / pose */
   expect_arg(slam_fundamental_lmeds(P, P, P, 16, 1, 0, 0, 0, P, P, P, NULL), "fm n_hyp=0");
   expect_arg(slam_fundamental_lmeds(NULL, P, P, 16, 1, 0, 0, 10, P, P, P, NULL), "fm null");
+  expect_arg(slam_fundamental_lmeds_ws(P, P, P, 16, 2, 0, 0, 10, P, P, P, P, 2 * 10 * 28 - 1, NULL),
+             "fm workspace too short");
+  expect_arg(slam_fundamental_lmeds_ws(P, P, P, 16, 2, 0, 0, 10, P, P, P, NULL, 2 * 10 * 28, NULL),
+             "fm null workspace");
+  expect(slam_fundamental_workspace_len(2, 10) == 2LL * 10 * 28, "fm workspace len");
+  expect(slam_fundamental_workspace_len(1 << 20, 4096) > 0, "fm workspace len no int overflow");
   expect_arg(slam_filter_pairs(P, P, P, -1, 1, P, P, NULL), "filter cap<0");
   expect_arg(slam_triangulate(P, P, P, 10, 1, P, P, 0, NULL, NULL), "tri null X");
   expect_arg(slam_pnp_ransac(P, P, P, 16, 1, P, 0, 0, 0, 2.0, 10, 10, P, P, P, P, P, 0, NULL),

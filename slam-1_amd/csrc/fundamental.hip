@@ -6,17 +6,20 @@
 // Hartley-normalised Gauss-Jordan null space, cubic roots, float errors,
 // min-median selection, OpenCV's robust sigma for the final inlier mask).
 //
-// k_fm_hyp: kSplit workgroups (8 waves) per frame pair, each a contiguous
-// range of the hypotheses:
-//   phase 1: one hypothesis per lane -> up to 3 candidate F in LDS;
-//   phase 2: wave w owns hypotheses h = w mod 8 of the range.  Per candidate the
-//            wave counts errors below its best median so far (exact reject: the
-//            median improves iff more than M/2 errors are below it); only
-//            improving candidates pay an exact radix-select median (4 x 8-bit
-//            passes, errors recomputed per pass instead of stored);
-//   phase 3: the workgroup's best (min median, lowest candidate index);
+// k_fm_solve: one hypothesis per lane (one-wave workgroups): the seeded sample
+//   and the 7-point solve -> up to 3 candidate F per hypothesis in a workspace.
+//   The solve needs the whole register file (the 7x9 system in f64), so it is
+//   a short kernel of its own rather than the first phase of the scoring one.
+// k_fm_score: kSplit workgroups (4 waves) per frame pair, each a contiguous
+//   range of the hypotheses, the pair's points staged in LDS.  Wave w owns
+//   every 4th hypothesis of the range.  Per candidate the wave counts errors
+//   below its best median so far (exact reject: the median improves iff more
+//   than M/2 errors are below it); only improving candidates pay an exact
+//   radix-select median (4 x 8-bit passes).  Then the workgroup's best (min
+//   median, lowest candidate index).  At most 128 VGPRs and 40 KB LDS, so two
+//   workgroups fit the half CU one ORB workgroup leaves free.
 // k_fm_finish: one workgroup per pair merges the kSplit bests by the same rule,
-//   recomputes the winner and writes the inlier mask.
+//   reads the winner from the workspace and writes the inlier mask.
 #include "common.hpp"
 
 #include <cmath>
@@ -26,10 +29,9 @@ namespace {
 #ifndef SLAM_FMH_WG
 #define SLAM_FMH_WG 256
 #endif
-// k_fm_hyp workgroup: its ~254-VGPR waves need a whole SIMD's register file two
-// at a time, so the size decides which CUs (next to ORB's waves or idle) take it
+// k_fm_score workgroup
 constexpr int kHWG = SLAM_FMH_WG, kHWaves = kHWG / 64;
-constexpr int kFWG = 64;  // k_fm_finish: one wave (lane 0 recomputes the winner, then the mask)
+constexpr int kFWG = 64;  // k_fm_finish: one wave
 constexpr int kS = 7;
 
 __device__ inline uint64_t splitmix64(uint64_t& s) {
@@ -300,16 +302,42 @@ __device__ __forceinline__ float fm_error(const double* F, const double* p1, con
   return isnan(e) ? INFINITY : e;
 }
 
+// The candidates travel from k_fm_solve to k_fm_score and k_fm_finish in a
+// caller-owned workspace: per (pair, hypothesis) a record of kRec doubles, the
+// candidate count (as a double) then up to 3 x 9 F entries.  Only records of
+// pairs with M >= 8 are written, and only those are read.
+constexpr int kRec = 28;
+constexpr int kSWG = 64;  // k_fm_solve: one wave, one hypothesis per lane
+
+__global__ __launch_bounds__(kSWG) void k_fm_solve(const double* __restrict__ m1all,
+                                                  const double* __restrict__ m2all,
+                                                  const int32_t* __restrict__ count, int cap,
+                                                  uint64_t seed, int item0, int n_hyp,
+                                                  double* __restrict__ ws) {
+  const int b = blockIdx.y, h = blockIdx.x * kSWG + threadIdx.x;
+  const int M = min(max(count[b], 0), cap);
+  if (M < 8 || h >= n_hyp) return;  // M < 8: k_fm_finish writes the empty mask
+  const double* m1 = m1all + (size_t)b * cap * 2;
+  const double* m2 = m2all + (size_t)b * cap * 2;
+  uint64_t s = seed ^ ((uint64_t)(item0 + b) * 0xD1B54A32D192ED03ull) ^
+               ((uint64_t)h * 0x9FB21C651E98DF25ull);
+  int idx[kS];
+  draw_sample(s, M, idx);
+  double* rec = ws + ((size_t)b * n_hyp + h) * kRec;
+  rec[0] = (double)seven_point(m1, m2, idx, reinterpret_cast<double (*)[9]>(rec + 1));
+}
+
 // Hypotheses of one frame pair are spread over kSplit workgroups (a
 // contiguous hypothesis range each), so a batch of B pairs fills B * kSplit
 // workgroups; each reports its best (median, candidate index) and k_fm_finish
-// merges them (min median, lowest index: the order-independent rule of the
-// single-workgroup form) and computes the mask.  The per-split bests travel in
-// F's own slot (72 B per pair), which k_fm_finish then overwrites.
+// merges them (min median, lowest index: an order-independent rule) and
+// computes the mask.  The per-split bests travel in F's own slot (72 B per
+// pair), which k_fm_finish then overwrites.
 constexpr int kSplit = 8;
-constexpr int kRound = 64;  // hypotheses per round (one per lane of wave 0)
-constexpr int kEv = 12;     // points per lane cached in registers (M <= 768 fully)
+constexpr int kEv = 12;        // errors per lane kept in registers for the select (M <= 768 fully)
+constexpr int kLdsPts = 1024;  // correspondences staged in LDS (32 B each); a larger M reads global
 static_assert(kSplit * 8 <= 9 * 8, "per-split bests must fit F[b]");
+static_assert(kLdsPts >= 64 * kEv, "the register-cached errors cover staged points first");
 #ifdef SLAM_FMH_TRACE
 __device__ unsigned long long g_fmh[8];
 #define FMH_T(i) do { if (threadIdx.x == 0 && blockIdx.x == 3 && blockIdx.y == 5) g_fmh[i] = __builtin_amdgcn_s_memtime(); } while (0)
@@ -317,132 +345,149 @@ __device__ unsigned long long g_fmh[8];
 #define FMH_T(i) (void)0
 #endif
 
-__global__ __launch_bounds__(kHWG) void k_fm_hyp(const double* __restrict__ m1all,
-                                                const double* __restrict__ m2all,
-                                                const int32_t* __restrict__ count, int cap,
-                                                uint64_t seed, int item0, int n_hyp,
-                                                double* __restrict__ Fout) {
-  __shared__ double cand[kRound][3][9];  // hypotheses processed in rounds of kRound
-  __shared__ int ncand[kRound];
+// the pair's correspondences, staged in LDS or read where they are
+struct PtsLds {
+  const double2* p1;
+  const double2* p2;
+  __device__ __forceinline__ float error(const double* F, int i) const {
+    const double2 a = p1[i], c = p2[i];
+    const double u[2] = {a.x, a.y}, v[2] = {c.x, c.y};
+    return fm_error(F, u, v);
+  }
+};
+struct PtsGlobal {
+  const double* m1;
+  const double* m2;
+  __device__ __forceinline__ float error(const double* F, int i) const {
+    return fm_error(F, m1 + 2 * i, m2 + 2 * i);
+  }
+};
+
+// Wave w scores hypotheses hb + w, hb + w + kHWaves, .. < he of its pair: per
+// candidate, the exact reject against the wave's best median so far (the
+// median improves iff more than M/2 errors are below it), then the exact
+// radix-select median of improving candidates only (4 x 8-bit passes).  w, hb
+// and he are wave-uniform.
+template <class Pts>
+__device__ __forceinline__ void fm_score_range(const Pts& pts, const double* __restrict__ recs,
+                                               int hb, int he, int w, int lane, int M, int* hist,
+                                               float& my_best, int& my_idx, int& n_cand,
+                                               int& n_sel) {
+  const int need = M / 2 + 1;  // #errors below a value for the median to be below it
+  for (int h = hb + w; h < he; h += kHWaves) {
+    const double* rec = recs + (size_t)h * kRec;
+    const int nc = (int)rec[0];
+    for (int k = 0; k < nc; ++k) {
+      double F[9];
+#pragma unroll
+      for (int i = 0; i < 9; ++i) F[i] = rec[1 + 9 * k + i];
+      // ln is opaque so that the point loads are not hoisted out of the
+      // hypothesis loop (they would stay live, 8 registers per point)
+      int ln = lane;
+      asm volatile("" : "+v"(ln));
+      int below = 0;
+      float ev[kEv];
+#pragma unroll
+      for (int j = 0; j < kEv; ++j) {
+        ev[j] = INFINITY;
+        if (ln + 64 * j < M) {
+          ev[j] = pts.error(F, ln + 64 * j);
+          below += ev[j] < my_best ? 1 : 0;
+        }
+      }
+      for (int i = ln + 64 * kEv; i < M; i += 64) below += pts.error(F, i) < my_best ? 1 : 0;
+      for (int off = 32; off > 0; off >>= 1) below += __shfl_xor(below, off, 64);
+      ++n_cand;
+      if (below < need) continue;  // median >= my_best: cannot improve (uniform)
+      ++n_sel;
+      // exact median = (M/2)-th smallest error, radix select on the float bits
+      uint32_t prefix = 0, pmask = 0;
+      int krank = M / 2;
+      for (int shift = 24; shift >= 0; shift -= 8) {
+        for (int j = lane; j < 256; j += 64) hist[j] = 0;
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int j = 0; j < kEv; ++j) {
+          const uint32_t bits = __float_as_uint(ev[j]);
+          if (ln + 64 * j < M && (bits & pmask) == prefix)
+            atomicAdd(&hist[(bits >> shift) & 255u], 1);
+        }
+        for (int i = ln + 64 * kEv; i < M; i += 64) {
+          const uint32_t bits = __float_as_uint(pts.error(F, i));
+          if ((bits & pmask) == prefix) atomicAdd(&hist[(bits >> shift) & 255u], 1);
+        }
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_s_waitcnt(0xC07F);
+        // prefix sums over 256 bins, 4 per lane
+        const int c0 = hist[4 * lane], c1 = hist[4 * lane + 1];
+        const int c2 = hist[4 * lane + 2], c3 = hist[4 * lane + 3];
+        const int sm = c0 + c1 + c2 + c3;
+        int inc = sm;
+        for (int off = 1; off < 64; off <<= 1) {
+          const int o = __shfl_up(inc, off, 64);
+          if (lane >= off) inc += o;
+        }
+        const int exc = inc - sm;
+        int bin = -1, before = 0;
+        if (krank >= exc && krank < inc) {
+          int acc = exc;
+          if (krank < acc + c0) { bin = 4 * lane; before = acc; }
+          else if (krank < acc + c0 + c1) { bin = 4 * lane + 1; before = acc + c0; }
+          else if (krank < acc + c0 + c1 + c2) { bin = 4 * lane + 2; before = acc + c0 + c1; }
+          else { bin = 4 * lane + 3; before = acc + c0 + c1 + c2; }
+        }
+        const unsigned long long bal = __ballot(bin >= 0);
+        const int src = __ffsll((long long)bal) - 1;
+        bin = __shfl(bin, src, 64);
+        before = __shfl(before, src, 64);
+        krank -= before;
+        prefix |= (uint32_t)bin << shift;
+        pmask |= 255u << shift;
+      }
+      const float med = __uint_as_float(prefix);
+      if (med < my_best) {
+        my_best = med;
+        my_idx = h * 3 + k;
+      }
+    }
+  }
+}
+
+// 4 waves per SIMD: at most 128 VGPRs
+__global__ __launch_bounds__(kHWG, 4) void k_fm_score(const double* __restrict__ m1all,
+                                                  const double* __restrict__ m2all,
+                                                  const int32_t* __restrict__ count, int cap,
+                                                  int n_hyp, const double* __restrict__ ws,
+                                                  double* __restrict__ Fout) {
+  __shared__ double2 sp1[kLdsPts], sp2[kLdsPts];
   __shared__ int hist[kHWaves][256];
   __shared__ float wbest[kHWaves];
   __shared__ int wbidx[kHWaves];
   const int b = blockIdx.x, sp = blockIdx.y, t = threadIdx.x;
-  const int lane = t & 63, w = t >> 6;
+  const int lane = t & 63, w = __builtin_amdgcn_readfirstlane(t >> 6);
   const int M = min(max(count[b], 0), cap);
   if (M < 8) return;  // k_fm_finish writes the empty mask
   const double* m1 = m1all + (size_t)b * cap * 2;
   const double* m2 = m2all + (size_t)b * cap * 2;
+  const double* recs = ws + (size_t)b * n_hyp * kRec;
   const int hb = (int)((long long)n_hyp * sp / kSplit), he = (int)((long long)n_hyp * (sp + 1) / kSplit);
   float my_best = INFINITY;
   int my_idx = 0x7FFFFFFF;
-  const int need = M / 2 + 1;  // #errors below a value for the median to be below it
+  int n_cand = 0, n_sel = 0;
   FMH_T(0);
-#ifdef SLAM_FMH_TRACE
-  int n_sel = 0, n_cand = 0;
-#endif
-  for (int h0 = hb; h0 < he; h0 += kRound) {
-    const int nh = min(kRound, he - h0);
-    __syncthreads();
-    if (t < nh) {
-      const int h = h0 + t;
-      uint64_t s = seed ^ ((uint64_t)(item0 + b) * 0xD1B54A32D192ED03ull) ^
-                   ((uint64_t)h * 0x9FB21C651E98DF25ull);
-      int idx[kS];
-      draw_sample(s, M, idx);
-      ncand[t] = seven_point(m1, m2, idx, cand[t]);
+  if (M <= kLdsPts) {
+    for (int i = t; i < M; i += kHWG) {
+      sp1[i] = make_double2(m1[2 * i], m1[2 * i + 1]);
+      sp2[i] = make_double2(m2[2 * i], m2[2 * i + 1]);
     }
     __syncthreads();
     FMH_T(1);
-    // the candidates' errors at the lane's points i = lane + 64 j (j < kEv) are
-    // kept in registers for the median select (points past 64 kEv: recomputed);
-    // ln is opaque so that their addresses are not hoisted (live) across the
-    // seven-point solves, which need the whole register file
-    int ln = lane;
-    asm volatile("" : "+v"(ln));
-    double pc[kEv][4];  // the points themselves, read once per round
-#pragma unroll
-    for (int j = 0; j < kEv; ++j) {
-      const int i = min(ln + 64 * j, M - 1);
-      pc[j][0] = m1[2 * i];
-      pc[j][1] = m1[2 * i + 1];
-      pc[j][2] = m2[2 * i];
-      pc[j][3] = m2[2 * i + 1];
-    }
-    for (int hl = w; hl < nh; hl += kHWaves) {
-      for (int k = 0; k < ncand[hl]; ++k) {
-        const double* F = cand[hl][k];
-        int below = 0;
-        float ev[kEv];
-#pragma unroll
-        for (int j = 0; j < kEv; ++j) {
-          ev[j] = INFINITY;
-          if (ln + 64 * j < M) {
-            ev[j] = fm_error(F, pc[j], pc[j] + 2);
-            below += ev[j] < my_best ? 1 : 0;
-          }
-        }
-        for (int i = ln + 64 * kEv; i < M; i += 64)
-          below += fm_error(F, m1 + 2 * i, m2 + 2 * i) < my_best ? 1 : 0;
-        for (int off = 32; off > 0; off >>= 1) below += __shfl_xor(below, off, 64);
-#ifdef SLAM_FMH_TRACE
-        ++n_cand;
-#endif
-        if (below < need) continue;  // median >= my_best: cannot improve (uniform)
-#ifdef SLAM_FMH_TRACE
-        ++n_sel;
-#endif
-        // exact median = (M/2)-th smallest error, radix select on the float bits
-        uint32_t prefix = 0, pmask = 0;
-        int krank = M / 2;
-        for (int shift = 24; shift >= 0; shift -= 8) {
-          for (int j = lane; j < 256; j += 64) hist[w][j] = 0;
-          __builtin_amdgcn_wave_barrier();
-#pragma unroll
-          for (int j = 0; j < kEv; ++j) {
-            const uint32_t bits = __float_as_uint(ev[j]);
-            if (ln + 64 * j < M && (bits & pmask) == prefix)
-              atomicAdd(&hist[w][(bits >> shift) & 255u], 1);
-          }
-          for (int i = ln + 64 * kEv; i < M; i += 64) {
-            const uint32_t bits = __float_as_uint(fm_error(F, m1 + 2 * i, m2 + 2 * i));
-            if ((bits & pmask) == prefix) atomicAdd(&hist[w][(bits >> shift) & 255u], 1);
-          }
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_s_waitcnt(0xC07F);
-          // prefix sums over 256 bins, 4 per lane
-          const int c0 = hist[w][4 * lane], c1 = hist[w][4 * lane + 1];
-          const int c2 = hist[w][4 * lane + 2], c3 = hist[w][4 * lane + 3];
-          const int sm = c0 + c1 + c2 + c3;
-          int inc = sm;
-          for (int off = 1; off < 64; off <<= 1) {
-            const int o = __shfl_up(inc, off, 64);
-            if (lane >= off) inc += o;
-          }
-          const int exc = inc - sm;
-          int bin = -1, before = 0;
-          if (krank >= exc && krank < inc) {
-            int acc = exc;
-            if (krank < acc + c0) { bin = 4 * lane; before = acc; }
-            else if (krank < acc + c0 + c1) { bin = 4 * lane + 1; before = acc + c0; }
-            else if (krank < acc + c0 + c1 + c2) { bin = 4 * lane + 2; before = acc + c0 + c1; }
-            else { bin = 4 * lane + 3; before = acc + c0 + c1 + c2; }
-          }
-          const unsigned long long bal = __ballot(bin >= 0);
-          const int src = __ffsll((long long)bal) - 1;
-          bin = __shfl(bin, src, 64);
-          before = __shfl(before, src, 64);
-          krank -= before;
-          prefix |= (uint32_t)bin << shift;
-          pmask |= 255u << shift;
-        }
-        const float med = __uint_as_float(prefix);
-        if (med < my_best) {
-          my_best = med;
-          my_idx = (h0 + hl) * 3 + k;
-        }
-      }
-    }
+    fm_score_range(PtsLds{sp1, sp2}, recs, hb, he, w, lane, M, hist[w], my_best, my_idx, n_cand,
+                   n_sel);
+  } else {
+    FMH_T(1);
+    fm_score_range(PtsGlobal{m1, m2}, recs, hb, he, w, lane, M, hist[w], my_best, my_idx, n_cand,
+                   n_sel);
   }
   FMH_T(2);
 #ifdef SLAM_FMH_TRACE
@@ -471,14 +516,12 @@ __global__ __launch_bounds__(kHWG) void k_fm_hyp(const double* __restrict__ m1al
 __global__ __launch_bounds__(kFWG) void k_fm_finish(const double* __restrict__ m1all,
                                                    const double* __restrict__ m2all,
                                                    const int32_t* __restrict__ count, int cap,
-                                                   uint64_t seed, int item0,
+                                                   int n_hyp, const double* __restrict__ ws,
                                                    uint8_t* __restrict__ mask,
                                                    double* __restrict__ Fout,
                                                    int32_t* __restrict__ ninl) {
-  __shared__ double Fb[9];
-  __shared__ double Fw[3][9];  // the winner's candidates, recomputed
   __shared__ float best_s;
-  __shared__ int found_s, cnt_s;
+  __shared__ int found_s, bidx_s, cnt_s;
   const int b = blockIdx.x, t = threadIdx.x;
   const int lane = t & 63;
   const int M = min(max(count[b], 0), cap);
@@ -505,20 +548,11 @@ __global__ __launch_bounds__(kFWG) void k_fm_finish(const double* __restrict__ m
     }
     best_s = bm;
     found_s = bi != 0x7FFFFFFF && bm < INFINITY;
+    bidx_s = bi;
     cnt_s = 0;
-    if (found_s) {
-      // recompute the winner
-      const int h = bi / 3, k = bi % 3;
-      uint64_t s = seed ^ ((uint64_t)(item0 + b) * 0xD1B54A32D192ED03ull) ^
-                   ((uint64_t)h * 0x9FB21C651E98DF25ull);
-      int idx[kS];
-      draw_sample(s, M, idx);
-      seven_point(m1, m2, idx, Fw);
-      for (int i = 0; i < 9; ++i) Fb[i] = Fw[k][i];
-    }
   }
   __syncthreads();
-  if (!found_s) {  // F[b] still holds k_fm_hyp's per-split slots: overwrite with 0
+  if (!found_s) {  // F[b] still holds k_fm_score's per-split slots: overwrite with 0
     for (int i = t; i < M; i += kFWG) mk[i] = 0;
     if (t < 9) Fout[9 * b + t] = 0.0;
     if (t == 0) ninl[b] = -1;
@@ -527,8 +561,11 @@ __global__ __launch_bounds__(kFWG) void k_fm_finish(const double* __restrict__ m
   double sigma = 2.5 * 1.4826 * (1 + 5.0 / (M - kS)) * sqrt((double)best_s);
   sigma = fmax(sigma, 0.001);
   const double thr = sigma * sigma;
+  // the winner's F as k_fm_solve wrote it
+  const int bi = bidx_s;
+  const double* Fw = ws + ((size_t)b * n_hyp + bi / 3) * kRec + 1 + 9 * (bi % 3);
   double F[9];
-  for (int i = 0; i < 9; ++i) F[i] = Fb[i];
+  for (int i = 0; i < 9; ++i) F[i] = Fw[i];
   int c = 0;
   for (int i = t; i < M; i += kFWG) {
     const uint8_t in = (double)fm_error(F, m1 + 2 * i, m2 + 2 * i) <= thr ? 1 : 0;
@@ -582,6 +619,37 @@ __global__ __launch_bounds__(kCWG) void k_filter_pairs(const int2* __restrict__ 
 
 }  // namespace
 
+extern "C" long long slam_fundamental_workspace_len(int batch, int n_hyp) {
+  return (long long)(batch > 0 ? batch : 0) * (n_hyp > 0 ? n_hyp : 0) * kRec;
+}
+
+extern "C" int slam_fundamental_lmeds_ws(const double* d_m1, const double* d_m2,
+                                         const int32_t* d_count, int cap, int batch,
+                                         uint64_t seed, int item0, int n_hyp, uint8_t* d_mask,
+                                         double* d_F, int32_t* d_ninliers, double* d_ws,
+                                         long long ws_len, void* stream) {
+  SLAM_REQUIRE(batch >= 0 && cap >= 0, "slam_fundamental_lmeds_ws: bad shape");
+  SLAM_REQUIRE(n_hyp >= 1 && n_hyp <= 4096, "slam_fundamental_lmeds_ws: n_hyp in [1, 4096]");
+  SLAM_REQUIRE(ws_len >= slam_fundamental_workspace_len(batch, n_hyp),
+               "slam_fundamental_lmeds_ws: workspace %lld < %lld doubles", ws_len,
+               slam_fundamental_workspace_len(batch, n_hyp));
+  if (batch == 0) return SLAM_OK;
+  SLAM_REQUIRE(d_m1 && d_m2 && d_count && d_mask && d_F && d_ninliers && d_ws,
+               "slam_fundamental_lmeds_ws: null pointer");
+  hipStream_t s = slam::as_stream(stream);
+  k_fm_solve<<<dim3((n_hyp + kSWG - 1) / kSWG, batch), kSWG, 0, s>>>(d_m1, d_m2, d_count, cap, seed,
+                                                                    item0, n_hyp, d_ws);
+  SLAM_LAUNCHED("k_fm_solve");
+  k_fm_score<<<dim3(batch, kSplit), kHWG, 0, s>>>(d_m1, d_m2, d_count, cap, n_hyp, d_ws, d_F);
+  SLAM_LAUNCHED("k_fm_score");
+  k_fm_finish<<<batch, kFWG, 0, s>>>(d_m1, d_m2, d_count, cap, n_hyp, d_ws, d_mask, d_F,
+                                    d_ninliers);
+  SLAM_LAUNCHED("k_fm_finish");
+  return SLAM_OK;
+}
+
+// The same three kernels on a workspace taken from, and returned to, the
+// stream's memory pool (stream-ordered: no synchronisation).
 extern "C" int slam_fundamental_lmeds(const double* d_m1, const double* d_m2,
                                       const int32_t* d_count, int cap, int batch, uint64_t seed,
                                       int item0, int n_hyp, uint8_t* d_mask, double* d_F,
@@ -592,12 +660,13 @@ extern "C" int slam_fundamental_lmeds(const double* d_m1, const double* d_m2,
   SLAM_REQUIRE(d_m1 && d_m2 && d_count && d_mask && d_F && d_ninliers,
                "slam_fundamental_lmeds: null pointer");
   hipStream_t s = slam::as_stream(stream);
-  k_fm_hyp<<<dim3(batch, kSplit), kHWG, 0, s>>>(d_m1, d_m2, d_count, cap, seed, item0, n_hyp, d_F);
-  SLAM_LAUNCHED("k_fm_hyp");
-  k_fm_finish<<<batch, kFWG, 0, s>>>(d_m1, d_m2, d_count, cap, seed, item0, d_mask, d_F,
-                                    d_ninliers);
-  SLAM_LAUNCHED("k_fm_finish");
-  return SLAM_OK;
+  const long long n = slam_fundamental_workspace_len(batch, n_hyp);
+  double* ws = nullptr;
+  SLAM_HIP(hipMallocAsync(reinterpret_cast<void**>(&ws), (size_t)n * sizeof(double), s));
+  const int rc = slam_fundamental_lmeds_ws(d_m1, d_m2, d_count, cap, batch, seed, item0, n_hyp,
+                                           d_mask, d_F, d_ninliers, ws, n, s);
+  SLAM_HIP(hipFreeAsync(ws, s));
+  return rc;
 }
 
 extern "C" int slam_filter_pairs(const int32_t* d_pairs, const int32_t* d_count,

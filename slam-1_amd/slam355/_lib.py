@@ -93,6 +93,9 @@ SIGNATURES = {
                            c_p, c_p, c_size_t, c_p],
     "slam_fundamental_lmeds": [c_p, c_p, c_p, c_int, c_int, c_uint64, c_int, c_int, c_p, c_p, c_p,
                                c_p],
+    "slam_fundamental_lmeds_ws": [c_p, c_p, c_p, c_int, c_int, c_uint64, c_int, c_int, c_p, c_p,
+                                  c_p, c_p, c_longlong, c_p],
+    "slam_fundamental_workspace_len": [c_int, c_int],
     "slam_filter_pairs": [c_p, c_p, c_p, c_int, c_int, c_p, c_p, c_p],
     "slam_ba_residual": [c_p, c_p, c_p, c_p, c_p, c_int, c_p, c_p],
     "slam_ba_jacobian": [c_p, c_p, c_p, c_p, c_p, c_int, c_p, c_p, c_p],
@@ -149,7 +152,9 @@ SIGNATURES = {
 }
 _RESTYPE = {"slam_last_error": ctypes.c_char_p, "slam_ba_sys_len": ctypes.c_longlong,
             "slam_ba_plan_bound": ctypes.c_longlong,
-            "slam_ba_chol_len": ctypes.c_longlong, "slam_pnp_workspace_len": ctypes.c_longlong, "slam_pose_chain_workspace_len": ctypes.c_longlong}
+            "slam_ba_chol_len": ctypes.c_longlong, "slam_pnp_workspace_len": ctypes.c_longlong,
+            "slam_fundamental_workspace_len": ctypes.c_longlong,
+            "slam_pose_chain_workspace_len": ctypes.c_longlong}
 
 
 class SlamError(RuntimeError):

@@ -46,8 +46,12 @@ def gather_temporal(X, ptl, kp_next, pairs, count, out=None, stream=None):
     return Q1, q2, q1
 
 
-def fundamental_lmeds(m1, m2, count, seed=0, item0=0, n_hyp=300, out=None, stream=None):
-    """m1/m2 [B,cap,2] f64 -> (mask [B,cap] u8, F [B,9] f64, ninliers [B] i32)."""
+def fundamental_lmeds(m1, m2, count, seed=0, item0=0, n_hyp=300, out=None, stream=None, ws=None):
+    """m1/m2 [B,cap,2] f64 -> (mask [B,cap] u8, F [B,9] f64, ninliers [B] i32).
+
+    ws: the candidate workspace (fundamental_workspace(B, n_hyp)); calls that may
+    run concurrently (other streams) must each pass their own.  Without one, the
+    library takes a stream-ordered buffer for this call."""
     B, cap, _ = m1.shape
     dev = m1.device
     if out is None:
@@ -56,10 +60,19 @@ def fundamental_lmeds(m1, m2, count, seed=0, item0=0, n_hyp=300, out=None, strea
         ninl = torch.zeros((B,), dtype=torch.int32, device=dev)
     else:
         mask, F, ninl = out
-    _lib.call("slam_fundamental_lmeds", ptr(m1), ptr(m2), ptr(count), cap, B,
-              int(seed) & ((1 << 64) - 1), int(item0), int(n_hyp), ptr(mask), ptr(F), ptr(ninl),
-              stream_ptr(stream))
+    args = (ptr(m1), ptr(m2), ptr(count), cap, B, int(seed) & ((1 << 64) - 1), int(item0),
+            int(n_hyp), ptr(mask), ptr(F), ptr(ninl))
+    if ws is None:
+        _lib.call("slam_fundamental_lmeds", *args, stream_ptr(stream))
+    else:
+        _lib.call("slam_fundamental_lmeds_ws", *args, ptr(ws), ws.numel(), stream_ptr(stream))
     return mask, F, ninl
+
+
+def fundamental_workspace(B, n_hyp=300, dev="cuda"):
+    """Candidate workspace of slam_fundamental_lmeds_ws for B pairs (f64)."""
+    n = int(_lib.lib.slam_fundamental_workspace_len(B, n_hyp))
+    return torch.empty(max(n, 1), dtype=torch.float64, device=dev)
 
 
 def filter_pairs(pairs, count, mask, out=None, stream=None):

@@ -86,6 +86,7 @@ class Tracker:
         self.p_ninl = torch.zeros((B,), **i32)
         self.p_mask = torch.zeros((B, cap), **u8)
         self.p_ws = geometry.pnp_workspace(B, dev=d)  # this Tracker's PnP hypotheses
+        self.f_ws = geometry.fundamental_workspace(B, dev=d)  # and its F-LMedS candidates
         self.imgs = torch.zeros((2 * B + 1, H, W), **u8)
         # device pose chain (main.py:120-124): (pose, T) carried across batches
         self.chain_state = torch.zeros((32,), **f64)
@@ -176,7 +177,7 @@ class Tracker:
         # F-LMedS mask (keypoint.py:59-66), then the surviving pairs with descriptors
         geometry.fundamental_lmeds(self.s_ptl, self.s_ptr, self.s_cnt, seed=self.seed,
                                    item0=frame0, out=(self.f_mask, self.f_F, self.f_ninl),
-                                   stream=st)
+                                   stream=st, ws=self.f_ws)
         mark("f_lmeds")
         geometry.filter_pairs(self.s_pairs, self.s_cnt, self.f_mask,
                               out=(self.f_pairs, self.f_cnt), stream=st)
