@@ -422,14 +422,28 @@ typedef struct slam_ba_problem {
   const int32_t* asm_act;
   int32_t n_asm_act;
   int32_t asm_pad;
+  /* Optional (null: every parameter free): held camera parameters, one word
+   * per camera [n_cams]; bit i (0..8: w0 w1 w2 t0 t1 t2 f k1 k2) set holds
+   * parameter i of that camera constant -- its column leaves the Jacobian
+   * (k_linearize / k_lin_mfma drop it from the 2 x 9 camera block of every
+   * observation), the LM iteration is otherwise unchanged, and its step is an
+   * exact zero (the held row of the reduced system keeps only its damped
+   * diagonal, lambda * 1e-6).  Gauge: hold the oldest keyframes whole (0x1FF);
+   * a calibrated camera: hold f, k1, k2 (0x1C0).  Landmark shards: every rank
+   * passes the same words.  Appended in ABI 1 (slam_abi_version() still
+   * returns 1): callers that zero the descriptor keep today's behaviour, and
+   * slam_ba_problem_size() tells a binding which layout a library has. */
+  const uint32_t* cam_fixed;
 } slam_ba_problem;
+/* sizeof(slam_ba_problem) of this library (400 with cam_fixed). */
+int slam_ba_problem_size(void);
 
 /* Largest tile count (tl_sched[1]) the dataflow tiled solve takes: one
  * persistent workgroup per tile column (they need not all be resident). */
 #define SLAM_TL_FLOW_MAX_T 256
 
 /* Problems per batched launch (slam_ba_iterate_batch splits larger batches).
- * The descriptors travel by value in the kernel arguments: 16 x 376 B
+ * The descriptors travel by value in the kernel arguments: 16 x 400 B
  * (ba.hip static_asserts the size; ROCm 7.2 takes this > 4 KB argument
  * segment, exercised by tests/test_ba.py's 16-window launch). */
 #ifndef SLAM_BA_MAX_BATCH

@@ -54,7 +54,7 @@ constexpr int kBS = 256;   // block size of the element-wise kernels
 // Batched LM: independent problems (local-BA windows) advance through one set
 // of launches, one problem per blockIdx.y; each keeps its own buffers and LM
 // state, so the iterates of a batched problem equal its solo iterates.  The
-// problem descriptors travel by value in the kernel arguments (16 x 392 B).
+// problem descriptors travel by value in the kernel arguments (16 x 400 B).
 constexpr int kBaMaxBatch = SLAM_BA_MAX_BATCH;
 struct BaBatch {
   slam_ba_problem p[kBaMaxBatch];
@@ -82,10 +82,10 @@ __device__ __forceinline__ int2 ba_xcd_map() {
   const int2 bw_ = ba_xcd_map();     \
   const int bx = bw_.x;              \
   const slam_ba_problem& p = (b).p[bw_.y]
-// the batch travels by value in the kernel arguments: 16 x 392 B,
+// the batch travels by value in the kernel arguments: 16 x 400 B,
 // beyond the traditional 4 KB; ROCm 7.2 takes it (tests/test_ba.py launches 16)
-static_assert(sizeof(slam_ba_problem) <= 392, "slam_ba_problem grew: re-check the kernarg size");
-static_assert(sizeof(BaBatch) <= 16 * 392, "BaBatch kernel argument size");
+static_assert(sizeof(slam_ba_problem) == 400, "slam_ba_problem grew: re-check the kernarg size");
+static_assert(sizeof(BaBatch) <= 16 * 400, "BaBatch kernel argument size");
 
 // The LM kernels are short and latency-bound and usually share their CUs with
 // the (throughput-bound) ORB workgroups of the concurrent tracking stream: they
@@ -245,6 +245,24 @@ __device__ __forceinline__ void clamp_rows(double r[2], double J[2][12]) {
       r[1] = r[1] / arc * half * 2.0;
     }
   }
+}
+
+// Held camera parameters (slam_ba_problem.cam_fixed): bit i of a camera's mask
+// word removes column i of the 2 x 9 camera block of its observations, before
+// the block enters any product, so the row and column of that parameter in the
+// reduced camera system are zero up to the damped diagonal and its step is an
+// exact zero.  (After the clamp: its chain rule is per column, 0 stays 0.)
+__device__ __forceinline__ void hold_cols(double J[2][12], unsigned fx) {
+#pragma unroll
+  for (int i = 0; i < 9; ++i)
+    if ((fx >> i) & 1u) J[0][i] = J[1][i] = 0.0;
+}
+// the two-lane form: half H holds camera columns 6 H .. 6 H + 5 (H = 1: 6..8)
+template <int H>
+__device__ __forceinline__ void hold_cols_half(double Jh[2][6], unsigned fx) {
+#pragma unroll
+  for (int i = 0; i < (H == 0 ? 6 : 3); ++i)
+    if ((fx >> (6 * H + i)) & 1u) Jh[0][i] = Jh[1][i] = 0.0;
 }
 
 // reproject_pre<true> + clamp_rows<true> split over two lanes by Jacobian
@@ -440,7 +458,7 @@ constexpr int kLinWG = 256;  // k_linearize: obs / point phases use kGrp lanes, 
 constexpr int kSlotLds = 128;  // slot ranges staged in LDS (larger groups read them from memory)
 constexpr int kPairLds = 1024; // observation pairs staged in LDS (ditto)
 
-// LDS of k_linearize (65 KB: leaves room for a co-resident ORB workgroup)
+// LDS of k_linearize (64.5 KiB: leaves room for a co-resident ORB workgroup)
 struct LinLds {
   double jc[kGrp][18];  // Jc rows (2 x 9)
   double w[kGrp][27];   // W = Jc^T Jp [i][c]; before phase 3: Jp (6), r (2)
@@ -451,6 +469,7 @@ struct LinLds {
   int cptr[kSlotLds];   // camera-slot ranges in cobs (when the group has < kSlotLds slots)
   int bptr[kSlotLds];   // block-slot ranges in pairs
   int pairs[kPairLds];  // the group's observation pairs (when <= kPairLds)
+  unsigned fx[kGrp];    // held-parameter mask of each observation's camera (cam_fixed only)
 };
 
 // Y_o row i (= W_o row i times V*^-1, V*^-1 symmetric) of a group observation
@@ -594,6 +613,27 @@ __global__ __launch_bounds__(kLinWG) void k_linearize(BaBatch bat) {
     L.lpt[t] = pt - p0;
   }
   __syncthreads();
+  if (p.cam_fixed != nullptr) {
+    // held parameters: each camera slot's mask word is loaded once and dealt to
+    // the slot's observations (the slots partition the group), then every
+    // observation lane drops the held columns of its camera block -- in its
+    // registers (W below) and in the LDS rows the slot phase reads
+    for (int sl = t; sl < ncs; sl += kLinWG) {
+      const unsigned fx = p.cam_fixed[p.cslot_cam[cs0 + sl]];
+      const int qe = p.cslot_obs_ptr[cs0 + sl + 1] - cb0;
+      for (int q = p.cslot_obs_ptr[cs0 + sl] - cb0; q < qe; ++q) L.fx[L.cobs[q]] = fx;
+    }
+    __syncthreads();
+    if (has) {
+      const unsigned fx = L.fx[t];
+      if (fx) {
+        hold_cols(J, fx);
+#pragma unroll
+        for (int i = 0; i < 9; ++i)
+          if ((fx >> i) & 1u) L.jc[t][i] = L.jc[t][9 + i] = 0.0;
+      }
+    }
+  }
   LIN_T(1);
   const double lam = p.state[SLAM_BA_ST_LAMBDA];
   if (t < p1 - p0) {
@@ -685,11 +725,13 @@ struct alignas(16) MLds {
   int la[kMObs];                 // supergroup-local camera of each observation
   int cobs[kMObs];               // chunk-local observations sorted by camera
   int cptr[8];                   // their per-camera runs
+  unsigned fx[kMCams];           // held-parameter mask word of each camera (cam_fixed only)
   int crow[kMCams];              // cpart row of each camera slot
   int bab[kMCams * (kMCams - 1) / 2], brow[kMCams * (kMCams - 1) / 2];  // block slots
 };
 static_assert(sizeof(MLds) <= 80 * 1024, "k_lin_mfma: two workgroups per CU");
 static_assert(9 * kMCams <= kMRows, "k_lin_mfma: 9m rows in 4 tile rows");
+static_assert(kMCams * kCamRec + kMCams <= kMWG, "k_lin_mfma: a lane per record entry and per mask word");
 static_assert(2 * kMPts * 3 * kMRows >= kMRows * kMRows + kMCams * 256, "staging aliases yt/wt");
 
 // -DSLAM_LINM_PROFILE: shader cycles per phase, summed over the workgroup's
@@ -885,11 +927,15 @@ __global__ __launch_bounds__(kMWG) void k_lin_mfma(BaBatch bat) {
   const int nt = (9 * m + 15) >> 4;  // tile rows of T
   const int cur = cur_of(p.state);
   const double lam = p.state[SLAM_BA_ST_LAMBDA];
+  const bool held = p.cam_fixed != nullptr;  // uniform: without a mask (A) takes no extra step
   // the supergroup's camera records -> LDS (one load per lane)
   if (t < kMCams * kCamRec) {
     const int a = t / kCamRec, k = t - kCamRec * (t / kCamRec);
     const int c = a < m ? sm[10 + a] : -1;
     if (c >= 0) L.cam[a][k] = p.camrec[cur][(size_t)kCamRec * c + k];
+  } else if (held && t - kMCams * kCamRec < m) {  // and their held-parameter words (the next lanes)
+    const int a = t - kMCams * kCamRec;
+    L.fx[a] = p.cam_fixed[sm[10 + a]];
   }
   if (t == 0) L.zero = 0.0;
   // output rows of this supergroup (read at the end; loaded now, off the tail)
@@ -1005,6 +1051,7 @@ __global__ __launch_bounds__(kMWG) void k_lin_mfma(BaBatch bat) {
         double r[2], Jh[2][6];
         if (t < 128) {
           reproject_half<0>(L.cam[L.la[k]], L.X[L.lpt[k]], q, r, Jh);
+          if (held) hold_cols_half<0>(Jh, L.fx[L.la[k]]);
 #pragma unroll
           for (int a = 0; a < 2; ++a) {
 #pragma unroll
@@ -1013,6 +1060,7 @@ __global__ __launch_bounds__(kMWG) void k_lin_mfma(BaBatch bat) {
           }
         } else {
           reproject_half<1>(L.cam[L.la[k]], L.X[L.lpt[k]], q, r, Jh);
+          if (held) hold_cols_half<1>(Jh, L.fx[L.la[k]]);
 #pragma unroll
           for (int a = 0; a < 2; ++a) {
 #pragma unroll
@@ -4055,6 +4103,8 @@ int check_problem(const slam_ba_problem* p) {
 }  // namespace
 
 extern "C" int slam_ba_red_slots(int n_grps) { return 2 * n_grps; }
+
+extern "C" int slam_ba_problem_size(void) { return (int)sizeof(slam_ba_problem); }
 
 extern "C" long long slam_ba_chol_len(int n_cams, const int32_t* tl_sched_host) {
   // tiled factor workspace (9C > kLdsMaxN) for a schedule of tl_sched_host[1]

@@ -135,13 +135,16 @@ def bundle_adjustment_sparsity(*args):
     return _bal_sparsity(*args)
 
 
-def bundle_adjustment_with_sparsity(*args):
+def bundle_adjustment_with_sparsity(*args, fixed=None):
     """bundle_adjustment_with_sparsity(car_params, sparse_mat) (:179, pose chain,
     ftol 0.1 as the reference) or (cam_params, Qs, cam_idxs, Q_idxs, qs,
-    sparse_mat) (:397, BAL).  Both return (residual_init, res.fun, res.x)."""
+    sparse_mat) (:397, BAL).  Both return (residual_init, res.fun, res.x).
+    fixed (BAL form only): camera parameters held constant, slam355.ba.fixed_mask."""
     if len(args) == 2:
+        if fixed is not None:
+            raise ValueError("fixed applies to the BAL form only")
         return _chain_solve(args[0], args[1], loop=True)
-    return _bal_with_sparsity(*args)
+    return _bal_with_sparsity(*args, fixed=fixed)
 
 
 # ----------------------------------------------------------------------------- BAL block
@@ -173,10 +176,10 @@ def _bal_sparsity(n_cams, n_Qs, cam_idxs, Q_idxs):
     return (A > 0).astype(int).tolil()
 
 
-def _solve(cam_params, Qs, cam_idxs, Q_idxs, qs, max_iters=200, ftol=1e-12):
+def _solve(cam_params, Qs, cam_idxs, Q_idxs, qs, max_iters=200, ftol=1e-12, fixed=None):
     cam_params = np.asarray(cam_params, np.float64).reshape(-1, 9)
     Qs = np.asarray(Qs, np.float64).reshape(-1, 3)
-    prob = _ba.BAProblem(cam_params, Qs, cam_idxs, Q_idxs, qs)
+    prob = _ba.BAProblem(cam_params, Qs, cam_idxs, Q_idxs, qs, fixed=fixed)
     params0 = np.hstack((cam_params.ravel(), Qs.ravel()))
     residual_init = _bal_objective(params0, len(cam_params), len(Qs), cam_idxs, Q_idxs, qs)
     prob.solve(max_iters=max_iters, ftol=ftol)
@@ -186,15 +189,16 @@ def _solve(cam_params, Qs, cam_idxs, Q_idxs, qs, max_iters=200, ftol=1e-12):
     return residual_init, fun, x
 
 
-def bundle_adjustment(cam_params, Qs, cam_idxs, Q_idxs, qs):
-    """(:372-377) -> (residual_init, res.fun, res.x)."""
-    return _solve(cam_params, Qs, cam_idxs, Q_idxs, qs)
+def bundle_adjustment(cam_params, Qs, cam_idxs, Q_idxs, qs, fixed=None):
+    """(:372-377) -> (residual_init, res.fun, res.x).  fixed: camera parameters
+    held constant (slam355.ba.fixed_mask: None, a [9] pattern, or [C, 9])."""
+    return _solve(cam_params, Qs, cam_idxs, Q_idxs, qs, fixed=fixed)
 
 
-def _bal_with_sparsity(cam_params, Qs, cam_idxs, Q_idxs, qs, sparse_mat):
+def _bal_with_sparsity(cam_params, Qs, cam_idxs, Q_idxs, qs, sparse_mat, fixed=None):
     """(:397-402) -> (residual_init, res.fun, res.x).  `sparse_mat` is checked
     for shape only: the GPU solver builds the same 2x12 block structure."""
     n = np.asarray(cam_params).size + np.asarray(Qs).size
     if sparse_mat is not None and tuple(sparse_mat.shape) != (2 * len(np.ravel(cam_idxs)), n):
         raise ValueError("sparse_mat shape does not match the problem")
-    return _solve(cam_params, Qs, cam_idxs, Q_idxs, qs)
+    return _solve(cam_params, Qs, cam_idxs, Q_idxs, qs, fixed=fixed)

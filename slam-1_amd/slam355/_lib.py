@@ -41,6 +41,7 @@ class BAProblemStruct(ctypes.Structure):
         ("sg_ptr", c_p), ("sg_meta", c_p), ("obs_meta", c_p), ("chk_optr", c_p), ("chk_cptr", c_p),
         ("bslot_ab", c_p), ("tl_sched", c_p), ("tl_sched_host", c_p), ("asm_tab", c_p),
         ("asm_act", c_p), ("n_asm_act", c_int), ("asm_pad", c_int),
+        ("cam_fixed", c_p),
     ]
 
 
@@ -100,6 +101,7 @@ SIGNATURES = {
     "slam_ba_residual": [c_p, c_p, c_p, c_p, c_p, c_int, c_p, c_p],
     "slam_ba_jacobian": [c_p, c_p, c_p, c_p, c_p, c_int, c_p, c_p, c_p],
     "slam_ba_red_slots": [c_int],
+    "slam_ba_problem_size": [],
     "slam_ba_sys_len": [c_int, c_int],
     "slam_ba_chol_len": [c_int, c_p],
     "slam_ba_build_system": [_PROB, c_p],

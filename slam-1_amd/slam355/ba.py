@@ -8,6 +8,11 @@ device.  Multi-GPU: each rank builds a BAProblem over ALL cameras and the
 observations of its own points; `step_distributed` all-reduces the reduced
 camera system (one RCCL all-reduce of ~(9C)^2 doubles) and two scalars per
 iteration.
+
+Held parameters: `fixed` (BAProblem, BAWindowSet.build / stage) names camera
+parameters that stay constant -- the gauge (the oldest keyframes held whole) or
+a calibrated camera's f, k1, k2 (FIXED_INTRINSICS); see fixed_mask.  Every rank
+of a sharded problem must pass the same mask.
 """
 from __future__ import annotations
 
@@ -39,6 +44,35 @@ def _check_indices(n_cams, n_pts, cam_idx, pt_idx, qs):
     if len(pt_idx) and (pt_idx.min() < 0 or pt_idx.max() >= n_pts):
         raise ValueError("point index out of range")
     return cam_idx, pt_idx, qs
+
+
+# ----------------------------------------------------------------------------- held parameters
+FIXED_INTRINSICS = np.array([0, 0, 0, 0, 0, 0, 1, 1, 1], np.uint8)  # hold f, k1, k2
+FIXED_CAMERA = np.ones(9, np.uint8)  # hold a camera whole (a gauge anchor)
+
+
+def fixed_mask(n_cams, fixed):
+    """The mask words of slam_ba_problem.cam_fixed: uint32 [n_cams], bit i
+    (0..8: w0 w1 w2 t0 t1 t2 f k1 k2) set = parameter i of that camera is held.
+    `fixed`: None (all free), a bool / 0-1 array [n_cams, 9], or a [9] pattern
+    applied to every camera.  A held parameter's column leaves the Jacobian:
+    its LM step is exactly zero, everything else about the iteration stays."""
+    n_cams = int(n_cams)
+    if fixed is None:
+        return np.zeros(n_cams, np.uint32)
+    f = np.asarray(fixed)
+    if f.dtype != np.bool_:
+        if f.dtype == object or not (np.issubdtype(f.dtype, np.integer) or
+                                     np.issubdtype(f.dtype, np.floating)):
+            raise ValueError("fixed must be a bool or 0/1 array")
+        if not np.all((f == 0) | (f == 1)):
+            raise ValueError("fixed must hold only 0 and 1 (or bool)")
+    if f.shape == (9,):
+        f = np.broadcast_to(f, (n_cams, 9))
+    elif f.shape != (n_cams, 9):
+        raise ValueError(f"fixed must have shape (9,) or ({n_cams}, 9), not {f.shape}")
+    bits = (f != 0).astype(np.uint32) << np.arange(9, dtype=np.uint32)
+    return np.ascontiguousarray(bits.sum(1, dtype=np.uint32))
 
 
 # ----------------------------------------------------------------------------- planner
@@ -990,8 +1024,12 @@ class BAProblem:
 
     def __init__(self, cams, pts, cam_idx, pt_idx, qs, *, lam0=1e-4, stream=None,
                  block_list=None, lin_mode="auto", chunks_per_wg=None, tl_mode="flow",
-                 fold_assembly=False, tile_mode=None, active_blocks=True):
-        """lin_mode: "mfma" (camera-union linearisation, k_lin_mfma: Schur
+                 fold_assembly=False, tile_mode=None, active_blocks=True, fixed=None):
+        """fixed: camera parameters held constant (fixed_mask: None, a [9]
+        pattern such as FIXED_INTRINSICS, or [C, 9]); `prob.fixed` is the
+        uint32 [C] mask (None when nothing is held).  With None every result
+        is the one a problem without the keyword gives.
+        lin_mode: "mfma" (camera-union linearisation, k_lin_mfma: Schur
         contraction on the f64 matrix cores; points renumbered internally),
         "slot" (k_linearize, any observation structure) or "auto" (mfma when
         every point is seen by <= MF_CAMS cameras).  The tiled camera solve
@@ -1015,6 +1053,7 @@ class BAProblem:
         pts = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
         C, P = len(cams), len(pts)
         cam_idx, pt_idx, qs = _check_indices(C, P, cam_idx, pt_idx, qs)
+        self.fixed = None if fixed is None else fixed_mask(C, fixed)
         pl = None
         if lin_mode in ("auto", "mfma"):
             pl = plan_mfma_native(C, P, cam_idx, pt_idx, block_list, chunks_per_wg)
@@ -1086,6 +1125,8 @@ class BAProblem:
         if self.tl_levels:
             t["tl_sched"] = T(self._sched_host)
         t["ticket"] = torch.zeros(1, dtype=torch.int32, device=dev)
+        if self.fixed is not None:
+            t["cam_fixed"] = T(self.fixed.view(np.int32))
         if stream is not None:  # the uploads and fills above ran on the current stream
             stream.wait_stream(torch.cuda.current_stream(dev))
         s = _Prob()
@@ -1104,6 +1145,8 @@ class BAProblem:
         if self.tl_levels:
             s.tl_sched = t["tl_sched"].data_ptr()
             s.tl_sched_host = self._sched_host.ctypes.data
+        if self.fixed is not None:
+            s.cam_fixed = t["cam_fixed"].data_ptr()
         if pl["mode"] == 1 and fold_assembly:  # k_lin_mfma assembles sys itself
             t["asm_tab"] = T(assembly_table(C, pl))
             s.asm_tab = t["asm_tab"].data_ptr()
@@ -1459,6 +1502,7 @@ class BAWindowSet:
         self.h = [None, None]  # (f64, i32, event) host staging per set
         self.gen = [0, 0]  # calls that have filled each set
         self.k = 0
+        self._fx = None  # (mask words, their device copy) of the last call with held parameters
 
     def _claim(self):
         """The set this call fills: its generation bumped (the problems of its
@@ -1475,6 +1519,24 @@ class BAWindowSet:
     @staticmethod
     def _al(n):
         return (max(int(n), 1) + 31) // 32 * 32
+
+    def _fixed_dev(self, sizes, fixed, stream):
+        """The device mask words of a call whose windows have `sizes` cameras:
+        one small buffer owned by the set, shared by the call's windows (a [9]
+        pattern: a word per camera of the largest window; [n, 9]: every window
+        has n cameras).  Kept while the mask stays the same and never
+        rewritten -- a new mask gets a new buffer, which the problems that
+        point at it keep alive -- so it needs no double buffering."""
+        if fixed is None or not sizes:
+            return None, None
+        f = np.asarray(fixed)
+        if f.ndim == 2 and any(c != f.shape[0] for c in sizes):
+            raise ValueError(f"fixed [{f.shape[0]}, 9] needs windows of {f.shape[0]} cameras")
+        words = fixed_mask(max(sizes), f)
+        if self._fx is None or not np.array_equal(self._fx[0], words):
+            with torch.cuda.stream(stream):
+                self._fx = (words, torch.from_numpy(words.view(np.int32)).to(self.dev))
+        return self._fx
 
     _F64 = ("cams0", "pts0", "cams1", "pts1", "init_c", "init_p", "obs_q", "camrec0", "camrec1",
             "cpart", "bpart", "sys", "chol", "delta_c", "red_part", "small", "state")
@@ -1496,7 +1558,7 @@ class BAWindowSet:
         offs = {k: int(m[base + i]) for i, k in enumerate(_lib.PLAN_TABLES)}
         return d64, d32, o64, int(m[9]), int(m[10]), offs
 
-    def stage(self, rows, cnt, maps, M, cams, u_off, v_off, stream, lam0=1e-4):
+    def stage(self, rows, cnt, maps, M, cams, u_off, v_off, stream, lam0=1e-4, fixed=None):
         """The tracked windows of one batch, staged by ONE native call
         (slam_ba_stage_windows: every window's observations from the mapper's
         rows, its plan, its float64 data and tables into the pinned staging
@@ -1505,7 +1567,10 @@ class BAWindowSet:
         maps [W, map_cap, 3], M [W], cams [B, 9] with B = W n; window w = pairs
         w n .. w n + n - 1.  Windows the camera-union plan cannot take are
         built as ordinary BAProblems (from the same host arrays).  Returns the
-        problems in window order (BAProblem interface)."""
+        problems in window order (BAProblem interface).  fixed: held camera
+        parameters, one [9] or [n, 9] pattern for every window of the call
+        (fixed_mask); its device words are written into the descriptors after
+        the native call, whose staged layout does not change."""
         rows = np.ascontiguousarray(rows, np.float64)
         cnt = np.ascontiguousarray(cnt, np.int32)
         maps = np.ascontiguousarray(maps, np.float64)
@@ -1516,6 +1581,7 @@ class BAWindowSet:
         if W == 0 or B % W or len(cams) != B or len(cnt) != B or len(M) != W:
             raise ValueError("stage: rows / cnt / cams must cover W windows of B / W pairs each")
         n = B // W
+        fwords, fdev = self._fixed_dev([n], fixed, stream)
         meta = np.zeros((W, self.META), np.int64)
         need = np.zeros(2, np.int64)
         probs = (_Prob * W)()
@@ -1568,7 +1634,7 @@ class BAWindowSet:
                 qs = np.stack([om[:, 2] - u_off, om[:, 3] - v_off], 1)
                 out.append(BAProblem(cams[w * n:w * n + n].copy(), maps[w, :int(M[w])].copy(),
                                      om[:, 0].astype(np.int64), om[:, 1].astype(np.int64), qs,
-                                     lam0=lam0, stream=stream))
+                                     lam0=lam0, stream=stream, fixed=fixed))
                 continue
             bp = self._window(slot)
             bp._t, bp._perm, bp._views = None, None, None
@@ -1577,13 +1643,22 @@ class BAWindowSet:
             bp.C, bp.P, bp.O, bp.stream = int(m[1]), int(m[2]), int(m[3]), stream
             bp.sys_len, bp.tl_levels = int(m[11]), False
             bp._s_raw = probs[w]
+            bp.fixed, bp._fixed_t = fwords, fdev
+            if fdev is not None:
+                bp._s_raw.cam_fixed = fdev.data_ptr()
             out.append(bp)
         built = [p for p in out if isinstance(p, _WindowProblem)]
         for i in range(0, len(built), BABatch.MAX_BATCH):
             BABatch(built[i:i + BABatch.MAX_BATCH], stream=stream).reset(lam0)
         return out
 
-    def build(self, problems, stream, lam0=1e-4):
+    def build(self, problems, stream, lam0=1e-4, fixed=None):
+        """The windows `problems` [(cams, pts, cam_idx, pt_idx, qs), ...] built
+        together (see the class); fixed: held camera parameters, one [9] or
+        [n, 9] pattern shared by every window of the call (fixed_mask)."""
+        problems = list(problems)
+        fwords, fdev = self._fixed_dev([len(np.reshape(pr[0], (-1, 9))) for pr in problems],
+                                       fixed, stream)
         specs, extra = [], []
         n64 = n32 = 0
         for w, (cams, pts, ci, pi, qs) in enumerate(problems):
@@ -1593,7 +1668,7 @@ class BAWindowSet:
             ci, pi, qs = _check_indices(C, P, ci, pi, qs)
             pl = plan_mfma_native(C, P, ci, pi) if 9 * C <= LDS_MAX_N else None
             if pl is None:
-                extra.append(BAProblem(cams, pts, ci, pi, qs, lam0=lam0, stream=stream))
+                extra.append(BAProblem(cams, pts, ci, pi, qs, lam0=lam0, stream=stream, fixed=fixed))
                 continue
             if pl["perm"] is not None:
                 pts = pts[pl["perm"]]
@@ -1671,6 +1746,10 @@ class BAWindowSet:
             for k in ("obs_q", "cpart", "bpart", "sys", "chol", "delta_c", "red_part", "small", "state"):
                 setattr(s, k, f64p(k))
             s.ticket = b32 + 4 * (o32 + nb + 4)
+            bp.fixed = None if fwords is None else fwords[:C]
+            bp._fixed_t = fdev
+            if fdev is not None:
+                s.cam_fixed = fdev.data_ptr()
             bp._s_raw = s
             out[w] = bp
         it = iter(extra)
