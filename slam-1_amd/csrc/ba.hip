@@ -419,8 +419,9 @@ __host__ __device__ __forceinline__ long long sys_vec_off(int n_cams, int n_bloc
 // Per point: V = sum Jp^T Jp and g = -sum Jp^T r over its observations, in
 // observation order (pt_acc per observation row), then V* = V + lam diag(V)
 // (diag clamped), V*^-1 by cofactors and e = V*^-1 g (pt_schur).  The
-// linearisers and k_back_trial run the same operations in the same order, so
-// the back substitution sees bit-identical V*^-1, e, g, diag.
+// linearisers and k_back_trial run the same operations in the same order on
+// every value (k_lin_mfma: one lane per component, pt_comp below), so the back
+// substitution sees bit-identical V*^-1, e, g, diag.
 struct PtSchur {
   double V00 = 0, V01 = 0, V02 = 0, V11 = 0, V12 = 0, V22 = 0, g0 = 0, g1 = 0, g2 = 0;
   double d[3], iv[6], e[3];
@@ -448,6 +449,40 @@ __device__ __forceinline__ void PtSchur::solve(double lam) {
   e[0] = iv[0] * g0 + iv[1] * g1 + iv[2] * g2;
   e[1] = iv[1] * g0 + iv[3] * g1 + iv[4] * g2;
   e[2] = iv[2] * g0 + iv[4] * g1 + iv[5] * g2;
+}
+
+// Component j of a point's (V00 V01 V02 V11 V12 V22 g0 g1 g2) over its
+// observations [kb, ke), rows a = 0, 1 of each in turn: the chain of rounded
+// products and sums PtSchur::acc runs for that component (g -= x y is
+// g += (-x) y, exactly), so a lane per (point, component) gives the bits one
+// lane per point gives.  jr: [8][stride], rows 0..5 Jp (2 x 3), 6..7 r.  The
+// operands of 4 observations are loaded before their sums are taken.
+__device__ __forceinline__ double pt_comp(const double* jr, int stride, int kb, int ke, int j) {
+  const int ia = j < 3 ? 0 : j < 5 ? 1 : j < 6 ? 2 : j - 6;
+  const int ib = j < 3 ? j : j < 5 ? j - 2 : 2;
+  const bool isg = j >= 6;
+  const double* xr[2] = {jr + ia * stride, jr + (3 + ia) * stride};
+  const double* yr[2] = {jr + (isg ? 6 : ib) * stride, jr + (isg ? 7 : 3 + ib) * stride};
+  double v = 0.0;
+  for (int k = kb; k < ke; k += 4) {
+    double x[4][2], y[4][2];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int kk = min(k + u, ke - 1);
+#pragma unroll
+      for (int a = 0; a < 2; ++a) {
+        x[u][a] = xr[a][kk];
+        y[u][a] = yr[a][kk];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (k + u >= ke) break;
+#pragma unroll
+      for (int a = 0; a < 2; ++a) v += (isg ? -x[u][a] : x[u][a]) * y[u][a];
+    }
+  }
+  return v;
 }
 
 constexpr int kCPart = 112;  // per camera slot: U - sum Y W^T (81), Jc^T r, Jc^T u, diag U (9 each), |r|^2, pad
@@ -704,6 +739,7 @@ __global__ __launch_bounds__(kLinWG) void k_linearize(BaBatch bat) {
 constexpr int kMObs = 120, kMPts = 16, kMCams = 7, kMRows = 64;
 constexpr int kMWG = 256;
 constexpr int kSgMeta = 24;  // sg_meta record: ch0 ch1 cs0 m bs0 nb p0 p1 o0 o1 cams[8] pad
+constexpr int kNoObs = 255;  // MLds::kfirst: the camera does not see the point
 constexpr int kMObsS = kMObs + 1;  // odd stride: element-major arrays read across lanes without conflicts
 struct alignas(16) MLds {
   // per-observation values stored element-major ([value][obs], stride 121):
@@ -725,11 +761,16 @@ struct alignas(16) MLds {
   int la[kMObs];                 // supergroup-local camera of each observation
   int cobs[kMObs];               // chunk-local observations sorted by camera
   int cptr[8];                   // their per-camera runs
+  uint8_t kfirst[kMPts][8];      // first observation of (point, camera slot) in the chunk, kNoObs: none
   unsigned fx[kMCams];           // held-parameter mask word of each camera (cam_fixed only)
   int crow[kMCams];              // cpart row of each camera slot
   int bab[kMCams * (kMCams - 1) / 2], brow[kMCams * (kMCams - 1) / 2];  // block slots
 };
 static_assert(sizeof(MLds) <= 80 * 1024, "k_lin_mfma: two workgroups per CU");
+static_assert(offsetof(MLds, ru) == offsetof(MLds, jp) + 6 * kMObsS * sizeof(double),
+              "k_lin_mfma: (B) reads Jp and r as the rows of one array");
+static_assert(kMObs <= kNoObs && kMCams <= 8 && kMPts * 8 <= kMWG, "k_lin_mfma: kfirst");
+static_assert(16 * kMPts <= kMWG && 2 * kMCams <= 16, "k_lin_mfma: 16 lanes per point in (B), (C)");
 static_assert(9 * kMCams <= kMRows, "k_lin_mfma: 9m rows in 4 tile rows");
 static_assert(kMCams * kCamRec + kMCams <= kMWG, "k_lin_mfma: a lane per record entry and per mask word");
 static_assert(2 * kMPts * 3 * kMRows >= kMRows * kMRows + kMCams * 256, "staging aliases yt/wt");
@@ -1002,6 +1043,21 @@ __global__ __launch_bounds__(kMWG) void k_lin_mfma(BaBatch bat) {
     no1 = p.chk_optr[ch0 + 2];
   }
   ChunkIn in = load_in(ch0, p0, p1, o0, o1);
+  // Y/W operand planes: rows >= 9m are zero for the workgroup's whole life --
+  // all planes are zeroed once here, (C) writes every row < 9m of the planes of
+  // a chunk's points (zeros for the cameras that do not see a point) and never
+  // a row >= 9m.  Planes of points >= npts hold what an earlier chunk left:
+  // the `on` predicate of (D) is the only guard against them.  (Was: all 64
+  // rows of a chunk's 3 npts planes zeroed per chunk, 49 KB of LDS stores.)
+  {
+    typedef double dbl2 __attribute__((ext_vector_type(2)));
+    dbl2* y2 = reinterpret_cast<dbl2*>(&L.yt[0][0][0]);
+    dbl2* w2 = reinterpret_cast<dbl2*>(&L.wt[0][0][0]);
+    for (int i = t; i < kMPts * 3 * kMRows / 2; i += kMWG) {
+      y2[i] = dbl2{0.0, 0.0};
+      w2[i] = dbl2{0.0, 0.0};
+    }
+  }
   for (int ch = ch0; ch < ch1; ++ch) {
     const int nobs = o1 - o0, npts = p1 - p0;
     const double q0 = in.q0, q1 = in.q1;
@@ -1014,21 +1070,17 @@ __global__ __launch_bounds__(kMWG) void k_lin_mfma(BaBatch bat) {
     if (t < 3 * npts) (&L.X[0][0])[t] = in.xv;
     if (t >= 128 && t - 128 <= npts) L.optr[t - 128] = in.pp;
     if (t < 8) L.cptr[t] = in.cp;
-    // Y/W operand planes of the chunk's points start at zero (rows of cameras
-    // a point is not seen by, rows >= 9m): all 64 rows of each of its 3 npts
-    // planes, one contiguous range, 16-byte stores (was: only the 16 nt rows
-    // of each plane through the rotation's index math -- 12 % of the kernel)
-    {
-      typedef double dbl2 __attribute__((ext_vector_type(2)));
-      dbl2* y2 = reinterpret_cast<dbl2*>(&L.yt[0][0][0]);
-      dbl2* w2 = reinterpret_cast<dbl2*>(&L.wt[0][0][0]);
-      const int n2 = npts * 3 * kMRows / 2;
-      for (int i = t; i < n2; i += kMWG) {
-        y2[i] = dbl2{0.0, 0.0};
-        w2[i] = dbl2{0.0, 0.0};
-      }
-    }
+    // the lane index as a value of this chunk: index math on threadIdx.x that
+    // the compiler hoists out of the chunk loop stays live through (A), the
+    // kernel's register peak (209 VGPRs against 183)
+    int tl = t;
+    asm volatile("" : "+v"(tl));
+    if (tl < kMPts * 8) (&L.kfirst[0][0])[tl] = kNoObs;
     __syncthreads();
+    // the first observation of each (point, camera) run (obs are sorted by
+    // point, then camera), for (C)
+    if (tl < nobs && (tl == 0 || L.lpt[tl - 1] != L.lpt[tl] || L.la[tl - 1] != L.la[tl]))
+      L.kfirst[L.lpt[tl]][L.la[tl]] = (uint8_t)tl;
     // prefetch: the next chunk's inputs and the extents of the one after
     int nnp0 = 0, nnp1 = 0, nno0 = 0, nno1 = 0;
     if (ch + 1 < ch1) {
@@ -1073,38 +1125,70 @@ __global__ __launch_bounds__(kMWG) void k_lin_mfma(BaBatch bat) {
     }
     __syncthreads();
     LINM_T(2);
-    // (B) per point: V, g, V* = V + lam diag(V), V*^-1 (cofactors), e = V*^-1 g
-    if (t < npts) {
+    // (B) per point: V, g, V* = V + lam diag(V), V*^-1 (cofactors), e = V*^-1 g.
+    //     Point lp has the 16 lanes 16 lp .. 16 lp + 15 (4 points per wave):
+    //     lane j < 9 sums component j of (V, g) (pt_comp: PtSchur::acc's chain
+    //     for it), the nine meet on the point's first lane by DPP row shifts (a
+    //     row is these 16 lanes), which solves (was: one lane per point, 16 of
+    //     256, nine chains each)
+    {
+      tl = t;  // again: not a value that lives through (A)
+      asm volatile("" : "+v"(tl));
+      const int lp = tl >> 4, j = tl & 15;
+      double v = 0.0;
+      if (lp < npts && j < 9) v = pt_comp(&L.jp[0][0], kMObsS, L.optr[lp], L.optr[lp + 1], j);
       PtSchur ps;
-      for (int k = L.optr[t]; k < L.optr[t + 1]; ++k) {
+      // row_shl:j -- lane i of a row takes lane i + j's value, so the row's lane 0
+      // takes component j (ds_bpermute would be an LDS round trip per dword)
+      auto row_lane = [](double x, auto sh) {
+        constexpr int kSh = decltype(sh)::value;
+        union { double d; int w[2]; } a, b;
+        a.d = x;
+        b.w[0] = __builtin_amdgcn_update_dpp(0, a.w[0], 0x100 + kSh, 0xF, 0xF, false);
+        b.w[1] = __builtin_amdgcn_update_dpp(0, a.w[1], 0x100 + kSh, 0xF, 0xF, false);
+        return b.d;
+      };
+      ps.V00 = v;
+      ps.V01 = row_lane(v, std::integral_constant<int, 1>{});
+      ps.V02 = row_lane(v, std::integral_constant<int, 2>{});
+      ps.V11 = row_lane(v, std::integral_constant<int, 3>{});
+      ps.V12 = row_lane(v, std::integral_constant<int, 4>{});
+      ps.V22 = row_lane(v, std::integral_constant<int, 5>{});
+      ps.g0 = row_lane(v, std::integral_constant<int, 6>{});
+      ps.g1 = row_lane(v, std::integral_constant<int, 7>{});
+      ps.g2 = row_lane(v, std::integral_constant<int, 8>{});
+      if (lp < npts && j == 0) {
+        ps.solve(lam);
 #pragma unroll
-        for (int a = 0; a < 2; ++a) ps.acc(L.jp[3 * a][k], L.jp[3 * a + 1][k], L.jp[3 * a + 2][k], L.ru[a][k]);
+        for (int k = 0; k < 3; ++k) L.e[lp][k] = ps.e[k];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) L.vi[lp][k] = ps.iv[k];
       }
-      ps.solve(lam);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) L.e[t][k] = ps.e[k];
-#pragma unroll
-      for (int k = 0; k < 6; ++k) L.vi[t][k] = ps.iv[k];
     }
     __syncthreads();
     LINM_T(3);
-    // (C) per observation, rows i of W~ split over two lanes (lane t: rows
-    //     0..4, lane t + 128: rows 5..8): W~_{p,a} rows summed over the run of
-    //     observations of the same (point, camera) (adjacent: obs are sorted by
-    //     point, then camera), Y = W~ V*^-1, into the operand planes; u_o.
+    // (C) per (point, camera): W~_{p,a} rows (h = 0: rows 0..4, h = 1: rows
+    //     5..8) summed over the run of observations of the same (point, camera)
+    //     (adjacent: obs are sorted by point, then camera), in observation
+    //     order, Y = W~ V*^-1, into the operand planes; per observation u_o.
+    //     Items (point lp, camera slot a < m, half h), lane 16 lp + 2 a + h: the
+    //     item takes the run of camera a in the point's observations (kfirst)
+    //     and writes its rows of the point's planes -- the values, or +0.0 when
+    //     camera a does not see the point, so every row < 9m of the chunk's
+    //     planes is written here and no pass has to zero them first.
     {
-      const int h = t >> 7, k0 = t & 127;
-      const bool lead = k0 < nobs && (k0 == 0 || L.lpt[k0 - 1] != L.lpt[k0] ||
-                                      L.la[k0 - 1] != L.la[k0]);
-      if (lead) {
-        const int lp = L.lpt[k0], a = L.la[k0];
-        const int ib = h ? 5 : 0, ie = h ? 9 : 5;
+      const int lp = tl >> 4, a = (tl & 15) >> 1, hh = tl & 1;
+      if (lp < npts && a < m) {
+        const int ke = L.optr[lp + 1];
+        const int kf = L.kfirst[lp][a];  // the run of camera a in the point's observations (staging)
+        const int ib = hh ? 5 : 0, ie = hh ? 9 : 5;
+        const bool seen = kf != kNoObs;
         double W[5][3];
 #pragma unroll
         for (int i = 0; i < 5; ++i)
 #pragma unroll
           for (int c = 0; c < 3; ++c) W[i][c] = 0.0;
-        for (int k = k0; k < nobs && L.lpt[k] == lp && L.la[k] == a; ++k) {
+        for (int k = kf; k < ke && L.la[k] == a; ++k) {
 #pragma unroll
           for (int i = 0; i < 5; ++i) {
             if (ib + i >= ie) break;
@@ -1122,11 +1206,13 @@ __global__ __launch_bounds__(kMWG) void k_lin_mfma(BaBatch bat) {
 #pragma unroll
           for (int c = 0; c < 3; ++c) {
             const int pos = (row + 16 * ((3 * lp + c) & 3)) & (kMRows - 1);  // see (D)
-            L.wt[lp][c][pos] = W[i][c];
-            L.yt[lp][c][pos] = W[i][0] * V[0][c] + W[i][1] * V[1][c] + W[i][2] * V[2][c];
+            const double y = W[i][0] * V[0][c] + W[i][1] * V[1][c] + W[i][2] * V[2][c];
+            L.wt[lp][c][pos] = W[i][c];   // +0.0 when not seen
+            L.yt[lp][c][pos] = seen ? y : 0.0;
           }
         }
       }
+      const int h = t >> 7, k0 = t & 127;
       if (h == 0 && k0 < nobs) {
         const double* e = L.e[L.lpt[k0]];
         L.ru[2][k0] = L.jp[0][k0] * e[0] + L.jp[1][k0] * e[1] + L.jp[2][k0] * e[2];
