@@ -738,21 +738,15 @@ __global__ __launch_bounds__(kLinWG) void k_linearize(BaBatch bat) {
 // sums.  Per point: V, g, V*, V*^-1, e (PtSchur, as k_linearize; LDS only).
 constexpr int kMObs = 120, kMPts = 16, kMCams = 7, kMRows = 64;
 constexpr int kMWG = 256;
+constexpr int kFoldWG = 256;   // lanes that sum in fold_rows_sum: fixes the order of the folded sums
 constexpr int kSgMeta = 24;  // sg_meta record: ch0 ch1 cs0 m bs0 nb p0 p1 o0 o1 cams[8] pad
 constexpr int kNoObs = 255;  // MLds::kfirst: the camera does not see the point
 constexpr int kMObsS = kMObs + 1;  // odd stride: element-major arrays read across lanes without conflicts
 struct alignas(16) MLds {
-  // per-observation values stored element-major ([value][obs], stride 121):
-  // lanes taking consecutive observations touch consecutive doubles, and the
-  // 16 lanes of an MFMA operand group (one observation, 16 values) stride by
-  // an odd number of doubles (was [obs][18]: 3 LDS conflict cycles per access)
-  double jc[18][kMObsS];         // Jc rows (2 x 9)
-  double jp[6][kMObsS];          // Jp rows (2 x 3)
-  double ru[4][kMObsS];          // r0 r1 u0 u1
+  // the small arrays first: their addresses fit the 16-bit offset field of an
+  // LDS instruction, so no register has to hold one across the chunk loop
   double vi[kMPts][6];           // V*^-1 (i00 i01 i02 i11 i12 i22)
   double e[kMPts][3];
-  double yt[kMPts][3][kMRows];   // Y_p, [point][k][row]: the MFMA A operand
-  double wt[kMPts][3][kMRows];   // W_p, [point][k][row]: the MFMA B operand
   double cam[kMCams][kCamRec];   // the supergroup's camera records (live parameters)
   double X[kMPts][3];            // the chunk's points
   double zero;                   // operand of padded MFMA lanes
@@ -765,34 +759,55 @@ struct alignas(16) MLds {
   unsigned fx[kMCams];           // held-parameter mask word of each camera (cam_fixed only)
   int crow[kMCams];              // cpart row of each camera slot
   int bab[kMCams * (kMCams - 1) / 2], brow[kMCams * (kMCams - 1) / 2];  // block slots
+  // per-observation values stored element-major ([value][obs], stride 121):
+  // lanes taking consecutive observations touch consecutive doubles, and the
+  // 16 lanes of an MFMA operand group (one observation, 16 values) stride by
+  // an odd number of doubles (was [obs][18]: 3 LDS conflict cycles per access)
+  alignas(8) double jc[18][kMObsS];  // Jc rows (2 x 9)
+  double jp[6][kMObsS];          // Jp rows (2 x 3)
+  double ru[4][kMObsS];          // r0 r1 u0 u1
+  alignas(16) double yt[kMPts][3][kMRows];  // Y_p, [point][k][row]: the MFMA A operand
+  double wt[kMPts][3][kMRows];   // W_p, [point][k][row]: the MFMA B operand
 };
 static_assert(sizeof(MLds) <= 80 * 1024, "k_lin_mfma: two workgroups per CU");
 static_assert(offsetof(MLds, ru) == offsetof(MLds, jp) + 6 * kMObsS * sizeof(double),
               "k_lin_mfma: (B) reads Jp and r as the rows of one array");
 static_assert(kMObs <= kNoObs && kMCams <= 8 && kMPts * 8 <= kMWG, "k_lin_mfma: kfirst");
 static_assert(16 * kMPts <= kMWG && 2 * kMCams <= 16, "k_lin_mfma: 16 lanes per point in (B), (C)");
+static_assert(kMWG == 256 && kMCams <= 7 && kMRows == 64, "k_lin_mfma: the deal of (D) covers 4 waves, 10 tiles and 7 cameras");
 static_assert(9 * kMCams <= kMRows, "k_lin_mfma: 9m rows in 4 tile rows");
 static_assert(kMCams * kCamRec + kMCams <= kMWG, "k_lin_mfma: a lane per record entry and per mask word");
-static_assert(2 * kMPts * 3 * kMRows >= kMRows * kMRows + kMCams * 256, "staging aliases yt/wt");
+static_assert(2 * kMPts * 3 * kMRows >= kMRows * kMRows + kMCams * 256 &&
+                  offsetof(MLds, wt) == offsetof(MLds, yt) + sizeof(MLds::yt),
+              "staging aliases yt/wt");
 
 // -DSLAM_LINM_PROFILE: shader cycles per phase, summed over the workgroup's
-// chunks (thread 0, s_memtime): 1 staging (incl. the wait for the prefetched
-// loads), 2 projections (A), 3 points (B), 4 W/Y (C), 5 MFMA + U (D),
+// chunks (first lane of wave SLAM_LINM_WAVE, s_memtime): 1 staging (incl. the
+// wait for the prefetched loads), 2 projections (A), 3 points (B), 4 W/Y (C), 5 MFMA + U (D),
 // 6 write-out (E); slam_linm_stamps reads them (scripts/linm_prof.py).
 #ifdef SLAM_LINM_PROFILE
+#ifndef SLAM_LINM_WAVE
+#define SLAM_LINM_WAVE 0  // the wave whose first lane takes the stamps (0..3)
+#endif
+#define LINM_ON (threadIdx.x == 64 * SLAM_LINM_WAVE)
 __device__ unsigned long long g_linm_stamp[4096][8];
-#define LINM_DECL() unsigned long long linm_prev = __builtin_amdgcn_s_memtime(), linm_acc[7] = {0, 0, 0, 0, 0, 0, 0}
-#define LINM_T(i)                                                  \
-  do {                                                             \
-    if (threadIdx.x == 0) {                                        \
+// (the sums live in LDS, not in registers of the kernel's peak)
+#define LINM_DECL()                                            \
+  __shared__ unsigned long long linm_acc[7];                   \
+  unsigned long long linm_prev = __builtin_amdgcn_s_memtime(); \
+  if (LINM_ON)                                                 \
+    for (int linm_i = 0; linm_i < 7; ++linm_i) linm_acc[linm_i] = 0
+#define LINM_T(i)                                                       \
+  do {                                                                  \
+    if (LINM_ON) {                                                      \
       const unsigned long long linm_now = __builtin_amdgcn_s_memtime(); \
-      linm_acc[i] += linm_now - linm_prev;                         \
-      linm_prev = linm_now;                                        \
-    }                                                              \
+      linm_acc[i] += linm_now - linm_prev;                              \
+      linm_prev = linm_now;                                             \
+    }                                                                   \
   } while (0)
 #define LINM_END()                                                               \
   do {                                                                           \
-    if (threadIdx.x == 0 && blockIdx.x + 1024 * blockIdx.y < 4096)               \
+    if (LINM_ON && blockIdx.x + 1024 * blockIdx.y < 4096)                        \
       for (int linm_i = 0; linm_i < 7; ++linm_i)                                 \
         g_linm_stamp[blockIdx.x + 1024 * blockIdx.y][linm_i] = linm_acc[linm_i]; \
   } while (0)
@@ -831,13 +846,13 @@ struct AsmTab {
   }
 };
 
-// out[e] (e < n) = sum over rows [rb, re) of part[row][e], with kMWG threads:
-// nparts = kMWG / n parts (rows rb + k, rb + k + nparts, ...; 4 loads in
-// flight), added in part order.  red: LDS [nparts][n].
+// out[e] (e < n) = sum over rows [rb, re) of part[row][e], on the workgroup's
+// first kFoldWG threads: nparts = kFoldWG / n parts (rows rb + k, rb + k +
+// nparts, ...; 4 loads in flight), added in part order.  red: LDS [nparts][n].
 __device__ void fold_rows_sum(const double* __restrict__ part, int stride, int rb, int re, int n,
                               double* red, double* out) {
   const int t = threadIdx.x;
-  const int nparts = kMWG / n, k = t / n, e = t - k * n;
+  const int nparts = kFoldWG / n, k = t / n, e = t - k * n;  // t >= kFoldWG: k >= nparts
   if (k < nparts) {
     double a[4] = {0.0, 0.0, 0.0, 0.0};
     int r = rb + k;
@@ -948,6 +963,113 @@ __device__ void lin_fold_assemble(const slam_ba_problem& p, const int* cams, int
   for (int q = 0; q < ndone; ++q) fold_block(p, done[q], scratch);
 }
 
+// The deal of (D)'s accumulation units -- the 10 upper 16x16 tiles of T (12
+// MFMAs per full chunk each) and the <= 7 camera tiles Z_a (8 each when the
+// camera sees all 16 points of a chunk) -- over the 4 waves (one per SIMD).
+// Dealt by measured time, not by MFMA count: a camera tile costs about 1.3
+// times a T tile (its operands come through the cobs indirection, its MFMAs
+// chain on one accumulator), and the first and last camera of a supergroup
+// see few points of most chunks (profiles/ba_waves/README.md).  Was
+// round-robin: 3 T + 2 Z on wave 0, a zero-fed third tile on waves 2 and 3.
+// A wave's tiles share a tile row I (waves 0, 1, 3) or a tile column J (wave
+// 2), so the shared operand is loaded once: 16 operand loads per K-group,
+// was 24.  One nibble per wave, 15: none.
+//   wave          0                1                2              3
+//   tiles (0,0)(0,1)(0,2)  (1,1)(1,2)(1,3)  (0,3)(2,3)(3,3)      (2,2)
+//   cams         5 6               3                2            0 1 4
+// A tile with I or J >= nt or a camera >= m does not exist: its wave holds
+// fewer units (the tiles and the cameras of a wave are listed so that those
+// that exist come first).  Accumulators: tiles in acc[0..2] and the cameras
+// in acc[3..4] on waves 0..2; the tile in acc[0] and the cameras in acc[1..3]
+// on wave 3.
+constexpr unsigned kDealI[3] = {0x2010u, 0x2210u, 0x2310u};   // tile s: I of wave w in nibble w
+constexpr unsigned kDealJ[3] = {0x2310u, 0xF321u, 0xF332u};
+constexpr unsigned kDealC[3] = {0x0235u, 0x1FF6u, 0x4FFFu};
+
+// (D), Schur part, for a wave with NTL tiles (I[s], J[s]) in u[0..NTL), which
+// share I (SHJ false) or J (SHJ true):
+// T += sum_p Y_p W_p^T as ONE product over the flat index kk = 3 lp + c
+// (point lp, coordinate c): K-step s of an MFMA takes kk = 4 s + k
+// (k = lane >> 4), so the 3 coordinates of consecutive points pack the K = 4
+// steps densely -- ceil(3 npts / 4) MFMAs per tile.  Plane kk stores row r at
+// (r + 16 (kk & 3)) mod 64, so the lane groups k = 0, 1 of an operand read
+// fall on different LDS banks:
+// A[i][k] = Y[16I + i][kk], B[k][j] = W[16J + j][kk], kk >= 3 npts -> 0.
+// Operands of 4 K-steps are loaded before their MFMAs are issued.
+template <int NTL, bool SHJ>
+__device__ __forceinline__ void linm_schur(const MLds& L, d4 (&u)[5], int nk, const int (&I)[3],
+                                           const int (&J)[3], int lane) {
+  const double* Yf = &L.yt[0][0][0];
+  const double* Wf = &L.wt[0][0][0];
+  const int mi = lane & 15, mk = lane >> 4;
+  constexpr int NA = SHJ ? NTL : 1, NB = SHJ ? 1 : NTL;
+  int ra[NA], rb[NB];
+#pragma unroll
+  for (int s = 0; s < NA; ++s) ra[s] = (16 * I[s] + mi + 16 * mk) & (kMRows - 1);
+#pragma unroll
+  for (int s = 0; s < NB; ++s) rb[s] = (16 * J[s] + mi + 16 * mk) & (kMRows - 1);
+  for (int k0 = 0; k0 < nk; k0 += 16) {
+    double av[4][NA], bv[4][NB];
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int kk = min(k0 + 4 * v + mk, 3 * kMPts - 1);
+#pragma unroll
+      for (int s = 0; s < NA; ++s) av[v][s] = Yf[kk * kMRows + ra[s]];
+#pragma unroll
+      for (int s = 0; s < NB; ++s) bv[v][s] = Wf[kk * kMRows + rb[s]];
+    }
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const bool on = k0 + 4 * v + mk < nk;
+#pragma unroll
+      for (int s = 0; s < NTL; ++s)
+        u[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(on ? av[v][SHJ ? s : 0] : 0.0, on ? bv[v][SHJ ? 0 : s] : 0.0,
+                                                    u[s], 0, 0, 0);
+    }
+  }
+}
+
+// (D), camera part, for a wave with NZA cameras cam[0..NZA) in u[B0..B0 + NZA):
+// Z_a += z^T z over camera a's observation rows, 2 observations per MFMA:
+// lane (i = lane & 15, k = lane >> 4) supplies z[row k & 1 of obs k >> 1][i]
+// as both operands (A[i][k] and B[k][i] take the same value).  The wave's
+// cameras advance together, 4 MFMAs each per step, operands loaded ahead;
+// past a camera's last observation: zeros.
+template <int B0, int NZA>
+__device__ __forceinline__ void linm_cams(const MLds& L, d4 (&u)[5], const int (&cam)[3], int lane) {
+  const int mi = lane & 15, mk = lane >> 4, row = mk & 1;
+  int qb[NZA], qe[NZA];
+  int nsteps = 0;
+#pragma unroll
+  for (int s = 0; s < NZA; ++s) {
+    qb[s] = __builtin_amdgcn_readfirstlane(L.cptr[cam[s]]);
+    qe[s] = __builtin_amdgcn_readfirstlane(L.cptr[cam[s] + 1]);
+    nsteps = max(nsteps, qe[s] - qb[s]);
+  }
+  for (int q = 0; q < nsteps; q += 8) {
+    double z[NZA][4];
+    bool ok[NZA][4];
+#pragma unroll
+    for (int s = 0; s < NZA; ++s)
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const int qq = qb[s] + q + 2 * v + (mk >> 1);
+        ok[s][v] = qq < qe[s];
+        const int k = L.cobs[ok[s][v] ? qq : 0];
+        const double* src = mi < 9 ? &L.jc[9 * row + mi][k]
+                            : mi < 11 ? &L.ru[row + 2 * (mi - 9)][k] : &L.zero;
+        z[s][v] = *src;
+      }
+#pragma unroll
+    for (int v = 0; v < 4; ++v)
+#pragma unroll
+      for (int s = 0; s < NZA; ++s) {
+        const double zv = ok[s][v] ? z[s][v] : 0.0;
+        u[B0 + s] = __builtin_amdgcn_mfma_f64_16x16x4f64(zv, zv, u[B0 + s], 0, 0, 0);
+      }
+  }
+}
+
 __global__ __launch_bounds__(kMWG) void k_lin_mfma(BaBatch bat) {
   BA_PROB_X(bat);
   const int sg = bx;
@@ -985,32 +1107,24 @@ __global__ __launch_bounds__(kMWG) void k_lin_mfma(BaBatch bat) {
     L.bab[t - 64] = p.bslot_ab[bs0 + t - 64];
     L.brow[t - 64] = p.bslot_row[bs0 + t - 64];
   }
-  // this wave's upper tiles of T (I <= J), dealt round-robin: <= 3 per wave;
-  // its cameras a = wid, wid + 4 (<= 2)
-  int tI[3], tJ[3];
-  int ntl = 0;
-  {
-    int s = 0;
-    for (int I = 0; I < nt; ++I)
-      for (int J = I; J < nt; ++J, ++s)
-        if ((s & 3) == wid && ntl < 3) {
-          tI[ntl] = I;
-          tJ[ntl] = J;
-          ++ntl;
-        }
-  }
-  const int nza = (m > wid) + (m > wid + 4);
-  int tRow[3], tCol[3];  // operand rows of this lane for each tile slot
+  // this wave's units (the deal above): tiles (tI[s], tJ[s]), s < ntl, cameras
+  // zc[s], s < nza
+  int tI[3], tJ[3], zc[3];
+  int ntl = 0, nza = 0;
 #pragma unroll
   for (int s = 0; s < 3; ++s) {
-    tRow[s] = 16 * (s < ntl ? tI[s] : 0) + (lane & 15);
-    tCol[s] = 16 * (s < ntl ? tJ[s] : 0) + (lane & 15);
+    tI[s] = (kDealI[s] >> (4 * wid)) & 15;
+    tJ[s] = (kDealJ[s] >> (4 * wid)) & 15;
+    ntl += tJ[s] < nt;
   }
-  d4 acc[3], zacc[2];
 #pragma unroll
-  for (int s = 0; s < 3; ++s) acc[s] = d4{0.0, 0.0, 0.0, 0.0};
+  for (int s = 0; s < 3; ++s) {
+    zc[s] = (kDealC[s] >> (4 * wid)) & 15;
+    nza += zc[s] < m;
+  }
+  d4 acc[5];
 #pragma unroll
-  for (int s = 0; s < 2; ++s) zacc[s] = d4{0.0, 0.0, 0.0, 0.0};
+  for (int s = 0; s < 5; ++s) acc[s] = d4{0.0, 0.0, 0.0, 0.0};
   const int mi = lane & 15, mk = lane >> 4;
 
   // chunk extents: the first from the record, the next loaded one chunk ahead;
@@ -1020,7 +1134,7 @@ __global__ __launch_bounds__(kMWG) void k_lin_mfma(BaBatch bat) {
     double q0, q1, xv;
     int meta, pp, cp;
   };
-  auto load_in = [&](int ch, int p0, int p1, int o0, int o1) {
+  auto load_in = [&](int t, int ch, int p0, int p1, int o0, int o1) {  // t: the lane (tl in the loop)
     ChunkIn in{0.0, 0.0, 0.0, 0, 0, 0};
     const int nobs = o1 - o0, npts = p1 - p0;
     const int ko = t & 127;  // (A) splits an observation over lanes t and t + 128
@@ -1042,7 +1156,7 @@ __global__ __launch_bounds__(kMWG) void k_lin_mfma(BaBatch bat) {
     no0 = p.chk_optr[ch0 + 1];
     no1 = p.chk_optr[ch0 + 2];
   }
-  ChunkIn in = load_in(ch0, p0, p1, o0, o1);
+  ChunkIn in = load_in(t, ch0, p0, p1, o0, o1);
   // Y/W operand planes: rows >= 9m are zero for the workgroup's whole life --
   // all planes are zeroed once here, (C) writes every row < 9m of the planes of
   // a chunk's points (zeros for the cameras that do not see a point) and never
@@ -1062,19 +1176,19 @@ __global__ __launch_bounds__(kMWG) void k_lin_mfma(BaBatch bat) {
     const int nobs = o1 - o0, npts = p1 - p0;
     const double q0 = in.q0, q1 = in.q1;
     __syncthreads();  // the previous chunk's readers are done with L
-    if (t < nobs) {
-      L.lpt[t] = in.meta & 255;
-      L.la[t] = (in.meta >> 8) & 255;
-      L.cobs[t] = in.meta >> 16;
-    }
-    if (t < 3 * npts) (&L.X[0][0])[t] = in.xv;
-    if (t >= 128 && t - 128 <= npts) L.optr[t - 128] = in.pp;
-    if (t < 8) L.cptr[t] = in.cp;
-    // the lane index as a value of this chunk: index math on threadIdx.x that
-    // the compiler hoists out of the chunk loop stays live through (A), the
-    // kernel's register peak (209 VGPRs against 183)
+    // the lane index as a value of this chunk: index and address math on
+    // threadIdx.x that the compiler hoists out of the chunk loop stays live
+    // through (A), the kernel's register peak
     int tl = t;
     asm volatile("" : "+v"(tl));
+    if (tl < nobs) {
+      L.lpt[tl] = in.meta & 255;
+      L.la[tl] = (in.meta >> 8) & 255;
+      L.cobs[tl] = in.meta >> 16;
+    }
+    if (tl < 3 * npts) (&L.X[0][0])[tl] = in.xv;
+    if (tl >= 128 && tl - 128 <= npts) L.optr[tl - 128] = in.pp;
+    if (tl < 8) L.cptr[tl] = in.cp;
     if (tl < kMPts * 8) (&L.kfirst[0][0])[tl] = kNoObs;
     __syncthreads();
     // the first observation of each (point, camera) run (obs are sorted by
@@ -1084,7 +1198,7 @@ __global__ __launch_bounds__(kMWG) void k_lin_mfma(BaBatch bat) {
     // prefetch: the next chunk's inputs and the extents of the one after
     int nnp0 = 0, nnp1 = 0, nno0 = 0, nno1 = 0;
     if (ch + 1 < ch1) {
-      in = load_in(ch + 1, np0, np1, no0, no1);
+      in = load_in(tl, ch + 1, np0, np1, no0, no1);
       if (ch + 2 < ch1) {
         nnp0 = p.grp_ptr[ch + 2];
         nnp1 = p.grp_ptr[ch + 3];
@@ -1097,7 +1211,7 @@ __global__ __launch_bounds__(kMWG) void k_lin_mfma(BaBatch bat) {
     //     split by Jacobian columns over lanes k and k + 128 (all 4 waves busy;
     //     was lanes 0..119 only)
     {
-      const int k = t & 127;
+      const int k = tl & 127;
       if (k < nobs) {
         const double q[2] = {q0, q1};
         double r[2], Jh[2][6];
@@ -1221,81 +1335,31 @@ __global__ __launch_bounds__(kMWG) void k_lin_mfma(BaBatch bat) {
     }
     __syncthreads();
     LINM_T(4);
-    // (D) T += sum_p Y_p W_p^T as ONE product over the flat index kk = 3 lp + c
-    //     (point lp, coordinate c): K-step s of an MFMA takes kk = 4 s + k
-    //     (k = lane >> 4), so the 3 coordinates of consecutive points pack the
-    //     K = 4 steps densely -- ceil(3 npts / 4) MFMAs per tile instead of one
-    //     per point with K padded 3 -> 4 (-25 %).  Plane kk stores row r at
-    //     (r + 16 (kk & 3)) mod 64, so the lane groups k = 0, 1 of an operand
-    //     read fall on different LDS banks:
-    //     A[i][k] = Y[16I + i][kk], B[k][j] = W[16J + j][kk], kk >= 3 npts -> 0.
-    //     Every wave issues 3 tile MFMAs per K-step (a wave with 2 tiles feeds
-    //     its third accumulator zeros), so the accumulators stay in their own
-    //     AGPRs with no control flow around the MFMAs; operands of 4 K-steps
-    //     are loaded before their MFMAs are issued.
+    // (D) this wave's units (the deal above; linm_schur, linm_cams): no MFMA
+    //     and no operand load for a unit the wave does not hold (was: a
+    //     zero-fed third tile on the waves with two).  wid, ntl and nza are
+    //     wave-uniform, so each wave runs one straight-line variant.
     {
-      const double* Yf = &L.yt[0][0][0];
-      const double* Wf = &L.wt[0][0][0];
       const int nk = 3 * npts;
-      for (int k0 = 0; k0 < nk; k0 += 16) {
-        double av[4][3], bv[4][3];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int kk = min(k0 + 4 * u + mk, 3 * kMPts - 1);
-#pragma unroll
-          for (int s = 0; s < 3; ++s) {
-            av[u][s] = Yf[kk * kMRows + ((tRow[s] + 16 * mk) & (kMRows - 1))];
-            bv[u][s] = Wf[kk * kMRows + ((tCol[s] + 16 * mk) & (kMRows - 1))];
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const bool on = k0 + 4 * u + mk < nk;
-#pragma unroll
-          for (int s = 0; s < 3; ++s) {
-            const bool o = on && s < ntl;
-            acc[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(o ? av[u][s] : 0.0, o ? bv[u][s] : 0.0,
-                                                         acc[s], 0, 0, 0);
-          }
-        }
+      int ld = lane;  // a value of this chunk, as tl: the operand addresses do not live through (A)
+      asm volatile("" : "+v"(ld));
+      if (wid == 2) {
+        if (ntl == 3) linm_schur<3, true>(L, acc, nk, tI, tJ, ld);
+      } else if (ntl == 3) {
+        linm_schur<3, false>(L, acc, nk, tI, tJ, ld);
+      } else if (ntl == 2) {
+        linm_schur<2, false>(L, acc, nk, tI, tJ, ld);
+      } else if (ntl == 1) {
+        linm_schur<1, false>(L, acc, nk, tI, tJ, ld);
       }
-    }
-    //     Z_a += z^T z over camera a's observation rows, 2 observations per MFMA:
-    //     lane (i = lane & 15, k = lane >> 4) supplies z[row k & 1 of obs k >> 1][i]
-    //     as both operands (A[i][k] and B[k][i] take the same value).  The
-    //     wave's two cameras (a = wid, wid + 4) advance together, 4 MFMAs each
-    //     per step, operands loaded ahead; missing cameras / observations: zeros.
-    {
-      const int row = mk & 1;
-      int qb[2], qe[2];
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const int a = wid + 4 * s;
-        qb[s] = s < nza ? L.cptr[a] : 0;
-        qe[s] = s < nza ? L.cptr[a + 1] : 0;
-      }
-      const int nsteps = max(qe[0] - qb[0], qe[1] - qb[1]);
-      for (int q = 0; q < nsteps; q += 8) {
-        double z[2][4];
-        bool ok[2][4];
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int qq = qb[s] + q + 2 * u + (mk >> 1);
-            ok[s][u] = qq < qe[s];
-            const int k = L.cobs[ok[s][u] ? qq : 0];
-            const double* src = mi < 9 ? &L.jc[9 * row + mi][k]
-                                : mi < 11 ? &L.ru[row + 2 * (mi - 9)][k] : &L.zero;
-            z[s][u] = *src;
-          }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-          for (int s = 0; s < 2; ++s) {
-            const double zv = ok[s][u] ? z[s][u] : 0.0;
-            zacc[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(zv, zv, zacc[s], 0, 0, 0);
-          }
+      if (wid == 3) {
+        if (nza == 3) linm_cams<1, 3>(L, acc, zc, ld);
+        else if (nza == 2) linm_cams<1, 2>(L, acc, zc, ld);
+        else if (nza == 1) linm_cams<1, 1>(L, acc, zc, ld);
+      } else if (nza == 2) {
+        linm_cams<3, 2>(L, acc, zc, ld);
+      } else if (nza == 1) {
+        linm_cams<3, 1>(L, acc, zc, ld);
       }
     }
     p0 = np0; p1 = np1; o0 = no0; o1 = no1;
@@ -1308,17 +1372,18 @@ __global__ __launch_bounds__(kMWG) void k_lin_mfma(BaBatch bat) {
   double* T = &L.yt[0][0][0];
   double* Z = T + kMRows * kMRows;  // [kMCams][16][16]
 #pragma unroll
-  for (int s = 0; s < 3; ++s) {
-    if (s >= ntl) break;
+  for (int s = 0; s < 5; ++s) {
+    const int ts = wid == 3 ? (s == 0 ? 0 : 3) : s;   // tile slot (3: none) and
+    const int zs = wid == 3 ? s - 1 : s - 3;          // camera slot (< 0: none) held by acc[s]
+    if (ts < 3 && ts < ntl) {
+      const int I = ts == 0 ? tI[0] : ts == 1 ? tI[1] : tI[2], J = ts == 0 ? tJ[0] : ts == 1 ? tJ[1] : tJ[2];
 #pragma unroll
-    for (int r = 0; r < 4; ++r)
-      T[(16 * tI[s] + mk + 4 * r) * kMRows + 16 * tJ[s] + mi] = acc[s][r];
-  }
+      for (int r = 0; r < 4; ++r) T[(16 * I + mk + 4 * r) * kMRows + 16 * J + mi] = acc[s][r];
+    } else if (zs >= 0 && zs < nza) {
+      const int a = zs == 0 ? zc[0] : zs == 1 ? zc[1] : zc[2];
 #pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    if (s >= nza) break;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) Z[(wid + 4 * s) * 256 + (mk + 4 * r) * 16 + mi] = zacc[s][r];
+      for (int r = 0; r < 4; ++r) Z[a * 256 + (mk + 4 * r) * 16 + mi] = acc[s][r];
+    }
   }
   __syncthreads();
   const bool fold = p.asm_tab != nullptr;  // uniform
