@@ -317,9 +317,8 @@ int slam_ba_jacobian(const double* d_cams, const double* d_pts, const int32_t* d
 #define SLAM_BA_ST_NACCEPT 9
 #define SLAM_BA_ST_PRED_CAM 10
 #define SLAM_BA_ST_CHOL_FAIL 11 /* last solve: 0 ok, 1 not SPD, 2 dataflow solve timed out */
-/* slots 12..15: phase timers of the profiling builds (SLAM_LIN_PROFILE,
- * SLAM_SOLVE_PROFILE; scripts/ba_solve_prof.py reads state[12:16]); slots 18, 19:
- * the per-panel timers of SLAM_SOLVE_PROFILE_PANEL (scripts/solve_trace.py) */
+/* slots 12..15: the phase timers of the -DSLAM_SOLVE_PROFILE build
+ * (scripts/ba_solve_prof.py reads state[12:16]); slots 17..19: unused */
 #define SLAM_BA_ST_SOLVE_FAULT 16 /* sticky: camera solves whose dataflow wait timed out
                                      * (fail code 2: a hang or a hand-off ordering bug --
                                      * the solve needs no co-residency, so a correct build

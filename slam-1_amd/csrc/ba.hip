@@ -601,18 +601,12 @@ __device__ __forceinline__ void lin_slots(const slam_ba_problem& p, LinLds& L, i
   }
 }
 
-#ifdef SLAM_LIN_PROFILE
-#define LIN_T(i) const uint64_t lin_t##i = __builtin_amdgcn_s_memtime()
-#else
-#define LIN_T(i) (void)0
-#endif
 __global__ __launch_bounds__(kLinWG) void k_linearize(BaBatch bat) {
   BA_PROB_X(bat);
   const int g = bx;
   if (g >= p.n_grps) return;  // batch: grid.x covers the largest problem
   lm_wave_priority();
   __shared__ LinLds L;
-  LIN_T(0);
   const int p0 = p.grp_ptr[g], p1 = p.grp_ptr[g + 1];
   const int o0 = p.pt_ptr[p0], o1 = p.pt_ptr[p1];
   const int t = threadIdx.x;
@@ -669,7 +663,6 @@ __global__ __launch_bounds__(kLinWG) void k_linearize(BaBatch bat) {
       }
     }
   }
-  LIN_T(1);
   const double lam = p.state[SLAM_BA_ST_LAMBDA];
   if (t < p1 - p0) {
     const int pt = p0 + t;
@@ -695,7 +688,6 @@ __global__ __launch_bounds__(kLinWG) void k_linearize(BaBatch bat) {
     L.ru[t][3] = J[1][9] * e[0] + J[1][10] * e[1] + J[1][11] * e[2];
   }
   __syncthreads();
-  LIN_T(2);
   // the group's slot lists (staged in LDS at kernel start: see below)
   // slot phase: LDS-staged lists when they fit (always at C3), else from memory
   // (two inlined copies, so every list access is a plain ds_read or global load)
@@ -704,17 +696,6 @@ __global__ __launch_bounds__(kLinWG) void k_linearize(BaBatch bat) {
   else
     lin_slots(p, L, cs0, ncs, bs0, nbs, p.cslot_obs_ptr + cs0, cb0, p.bslot_pair_ptr + bs0, pb0,
               p.bslot_pairs + pb0);
-#ifdef SLAM_LIN_PROFILE
-  __builtin_amdgcn_s_waitcnt(0);
-  __syncthreads();
-  LIN_T(3);
-  if (g == 7 && t == 0) {
-    p.state[12] = (double)(lin_t1 - lin_t0);
-    p.state[13] = (double)(lin_t2 - lin_t1);
-    p.state[14] = (double)(lin_t3 - lin_t2);
-    p.state[15] = (double)(ncs * 100 + nbs);
-  }
-#endif
 }
 
 // ---------------------------------------------------------------- camera-union linearisation
@@ -846,37 +827,55 @@ struct AsmTab {
   }
 };
 
-// out[e] (e < n) = sum over rows [rb, re) of part[row][e], on the workgroup's
-// first kFoldWG threads: nparts = kFoldWG / n parts (rows rb + k, rb + k +
-// nparts, ...; 4 loads in flight), added in part order.  red: LDS [nparts][n].
-__device__ void fold_rows_sum(const double* __restrict__ part, int stride, int rb, int re, int n,
-                              double* red, double* out) {
+// (a[0] + a[1]) + (a[2] + a[3]), ... : the fixed tree over N = 2^k values
+template <int N>
+__device__ __forceinline__ double pair_sum(const double* a) {
+  if constexpr (N == 1) return a[0];
+  else return pair_sum<N / 2>(a) + pair_sum<N / 2>(a + N / 2);
+}
+
+// Column sums of the n-wide rows [rb, re) of part (row stride `stride`), on the
+// workgroup's first WG threads (a thread t >= WG gets k >= nparts): the lanes
+// are (part k, column e) pairs; part k takes rows rb + k, rb + k + nparts, ...
+// with NF loads in flight (sc1 loads when SC1: rows that other workgroups
+// wrote in this launch), then the parts are added in order k = 0, 1, ...
+// (deterministic).  red: LDS [nparts] rows of RS doubles (RS = 0: of n).
+// Result in out[0..n).  The folded assembly (kFoldWG lanes, 4 loads, sc1) and
+// k_assemble (kAsmWG lanes, 8 loads) sum in different orders: each form gives
+// its own bits.
+template <int WG, int NF, bool SC1, int RS>
+__device__ void rows_sum(const double* __restrict__ part, int stride, int rb, int re, int n,
+                         double* red, double* out) {
   const int t = threadIdx.x;
-  const int nparts = kFoldWG / n, k = t / n, e = t - k * n;  // t >= kFoldWG: k >= nparts
+  const int nparts = WG / n, k = t / n, e = t - k * n;
+  const int rs = RS ? RS : n;
+  auto ld = [](const double* q) { return SC1 ? ld_sc1(q) : *q; };
   if (k < nparts) {
-    double a[4] = {0.0, 0.0, 0.0, 0.0};
+    double a[NF] = {};
     int r = rb + k;
-    for (; r + 3 * nparts < re; r += 4 * nparts) {
-      double v[4];
+    for (; r + (NF - 1) * nparts < re; r += NF * nparts) {
+      double v[NF];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = ld_sc1(part + (size_t)(r + u * nparts) * stride + e);
+      for (int u = 0; u < NF; ++u) v[u] = ld(part + (size_t)(r + u * nparts) * stride + e);
 #pragma unroll
-      for (int u = 0; u < 4; ++u) a[u] += v[u];
+      for (int u = 0; u < NF; ++u) a[u] += v[u];
     }
-    for (int u = 0; r < re; r += nparts, ++u) a[u] += ld_sc1(part + (size_t)r * stride + e);
-    red[k * n + e] = (a[0] + a[1]) + (a[2] + a[3]);
+    for (int u = 0; r < re; r += nparts, ++u) a[u] += ld(part + (size_t)r * stride + e);
+    red[k * rs + e] = pair_sum<NF>(a);
   }
   __syncthreads();
   if (t < n) {
     double v = 0.0;
-    for (int q = 0; q < nparts; ++q) v += red[q * n + t];
+    for (int q = 0; q < nparts; ++q) v += red[q * rs + t];
     out[t] = v;
   }
   __syncthreads();
 }
 
-// sys block blk (+ its camera's vectors when diagonal) from the partial rows;
-// the same formulas as k_assemble
+// sys block blk (+ its camera's vectors when diagonal) from the partial rows
+// (sc1 loads, 4 in flight, the parts n apart in red).  The write-out after the
+// sums repeats k_assemble's statement for statement: as one shared function it
+// changed both kernels' instructions (profiles/ba_dead_knobs/README.md).
 __device__ void fold_block(const slam_ba_problem& p, int blk, double* scratch) {
   double* red = scratch;             // [<= 3][112]
   double* sh = scratch + 3 * kCPart;  // [112]
@@ -890,9 +889,10 @@ __device__ void fold_block(const slam_ba_problem& p, int blk, double* scratch) {
   double* costc = diagU + C9;
   const bool diag = c1 == c2;
   const int bb = p.blk_bslot_ptr[blk], be = p.blk_bslot_ptr[blk + 1];
-  if (diag) fold_rows_sum(p.cpart, kCPart, p.cam_cslot_ptr[c1], p.cam_cslot_ptr[c1 + 1], 109, red, sh);
+  if (diag)
+    rows_sum<kFoldWG, 4, true, 0>(p.cpart, kCPart, p.cam_cslot_ptr[c1], p.cam_cslot_ptr[c1 + 1], 109, red, sh);
   if (be > bb) {
-    fold_rows_sum(p.bpart, 81, bb, be, 81, red, sb);
+    rows_sum<kFoldWG, 4, true, 0>(p.bpart, 81, bb, be, 81, red, sb);
   } else if (t < 81) {
     sb[t] = 0.0;
   }
@@ -1426,40 +1426,11 @@ __global__ __launch_bounds__(kMWG) void k_lin_mfma(BaBatch bat) {
   LINM_END();
 }
 
-// Column sums of the n-wide rows [rb, re) of part (row stride `stride`): the
-// workgroup's lanes are (part k, column e) pairs; part k takes rows rb + k,
-// rb + k + nparts, ... with 8 loads in flight, then the parts are added in
-// order k = 0, 1, ... (deterministic).  Result in out[0..n).
 #ifndef SLAM_ASM_WG
 #define SLAM_ASM_WG 1024  // k_assemble workgroup (>= 128: one lane per element of a 109-double row)
 #endif
 constexpr int kAsmWG = SLAM_ASM_WG;
 static_assert(kAsmWG >= 128 && kAsmWG % 64 == 0, "SLAM_ASM_WG");
-__device__ void rows_sum(const double* __restrict__ part, int stride, int rb, int re, int n,
-                         double (*red)[kCPart], double* out) {
-  const int t = threadIdx.x;
-  const int nparts = kAsmWG / n, k = t / n, e = t - k * n;
-  if (k < nparts) {
-    double a[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int r = rb + k;
-    for (; r + 7 * nparts < re; r += 8 * nparts) {
-      double v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) v[u] = part[(size_t)(r + u * nparts) * stride + e];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) a[u] += v[u];
-    }
-    for (int u = 0; r < re; r += nparts, ++u) a[u] += part[(size_t)r * stride + e];
-    red[k][e] = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-  }
-  __syncthreads();
-  if (t < n) {
-    double v = 0.0;
-    for (int q = 0; q < nparts; ++q) v += red[q][t];
-    out[t] = v;
-  }
-  __syncthreads();
-}
 
 // One workgroup per upper camera-pair block (c1 <= c2), ALL C(C+1)/2 of them.
 // The slot partials of a camera / block are contiguous rows (the planner's
@@ -1522,13 +1493,17 @@ __global__ __launch_bounds__(kAsmWG) void k_assemble(BaBatch bat) {
     }
     return;
   }
-  if (diag) rows_sum(p.cpart, kCPart, p.cam_cslot_ptr[c1], p.cam_cslot_ptr[c1 + 1], 109, red, sh);
+  // plain loads, 8 in flight, the parts in rows of red
+  if (diag)
+    rows_sum<kAsmWG, 8, false, kCPart>(p.cpart, kCPart, p.cam_cslot_ptr[c1], p.cam_cslot_ptr[c1 + 1], 109,
+                                       &red[0][0], sh);
   if (!diag || be > bb) {
-    rows_sum(p.bpart, 81, bb, be, 81, red, sb);
+    rows_sum<kAsmWG, 8, false, kCPart>(p.bpart, 81, bb, be, 81, &red[0][0], sb);
   } else if (t < 81) {
     sb[t] = 0.0;
   }
   __syncthreads();
+  // the block write-out (the same statements in fold_block: see there)
   if (sys_packed(p.n_cams)) {
     if (t < 81) S[(size_t)blk * 81 + t] = diag ? sh[t] - (sb[t] + sb[9 * (t % 9) + t / 9]) : -sb[t];
   } else if (t < 81) {
@@ -1664,7 +1639,8 @@ __device__ void solve_epilogue(const slam_ba_problem& p, const double* x, bool o
 }
 
 // -DSLAM_SOLVE_PROFILE: phase timestamps (wall_clock64, 100 MHz) of k_solve_blk
-// into the spare LM state slots 12..15 (ns): load, eliminate, back-substitute, epilogue.
+// into the spare LM state slots 12..15 (ns): load, eliminate, back-substitute,
+// epilogue (scripts/ba_solve_prof.py reads them).
 #ifdef SLAM_SOLVE_PROFILE
 #define SOLVE_PROF_T(i) uint64_t prof_t##i = wall_clock64()
 #define SOLVE_PROF_END()                                                        \
@@ -1743,6 +1719,9 @@ struct BlkLds {
   }
 };
 
+// -DSLAM_SOLVE_TRACE: s_memtime of problem 0's thread 0 at the points of each
+// block step (rows 0..17; 18, 19: after the loop and the load); slam_solve_trace
+// reads them (scripts/solve_trace.py).
 #ifdef SLAM_SOLVE_TRACE
 __device__ unsigned long long g_solve_trace[20][6];
 #define SOLVE_TR(step, i)                                                        \
@@ -1894,9 +1873,6 @@ __global__ __launch_bounds__(kBlkWG) __attribute__((amdgpu_waves_per_eu(2))) voi
   SOLVE_TR(19, 0);
   for (int c0 = 0; c0 < n; c0 += kPanelW) {
     SOLVE_TR(c0 / kPanelW, 0);
-#ifdef SLAM_SOLVE_PROFILE_STEP
-    const uint64_t q0 = __builtin_amdgcn_s_memtime();
-#endif
     // (a) panel columns [c0, c0 + 9), rows c0..n -> Pn[row - c0][col - c0]
 #pragma unroll
     for (int s = 0; s < kTileMax; ++s) {
@@ -1912,9 +1888,6 @@ __global__ __launch_bounds__(kBlkWG) __attribute__((amdgpu_waves_per_eu(2))) voi
     }
     __syncthreads();
     SOLVE_TR(c0 / kPanelW, 1);
-#ifdef SLAM_SOLVE_PROFILE_STEP
-    const uint64_t q1 = __builtin_amdgcn_s_memtime();
-#endif
     // (b) panel factorisation, one panel row per lane: lanes 0..8 of every
     // participating wave hold the 9 pivot rows r = c0 + m (lower entries),
     // lanes 9..63 of wave w the rows c0 + 9 + 55 w + (lane - 9) (the rhs row n
@@ -1944,10 +1917,6 @@ __global__ __launch_bounds__(kBlkWG) __attribute__((amdgpu_waves_per_eu(2))) voi
       for (int j = 0; j < kPanelW; ++j) u[j] = valid && (!piv || j <= rl) ? pr[j] : 0.0;
       double Dinv[kPanelW];
       bool bad = false;
-#ifdef SLAM_SOLVE_PROFILE_PANEL
-      __builtin_amdgcn_s_waitcnt(0);
-      const uint64_t qb1 = __builtin_amdgcn_s_memtime();
-#endif
       static_for<0, kPanelW>([&](auto J) {
         constexpr int j = decltype(J)::value;
         const double d = bcast16<j>(u[j]);
@@ -1957,18 +1926,6 @@ __global__ __launch_bounds__(kBlkWG) __attribute__((amdgpu_waves_per_eu(2))) voi
         if constexpr (j + 1 < kPanelW) u[j + 1] = __builtin_fma(-l, bcast16<j + 1>(u[j]), u[j + 1]);
         PanelRest<j>::run(u, u[j], -l);
       });
-#ifdef SLAM_SOLVE_PROFILE_PANEL
-      {
-        double chk = u[kPanelW - 1];
-        __asm__ volatile("" : "+v"(chk));
-        u[kPanelW - 1] = chk;
-      }
-      const uint64_t qb2 = __builtin_amdgcn_s_memtime();
-      if (t == 0 && c0 == 9 * (n / 18)) {
-        p.state[SLAM_BA_ST_SLOTS - 2] = (double)(qb1 - q1);  // replaces barrier / (c)
-        p.state[SLAM_BA_ST_SLOTS - 1] = (double)(qb2 - qb1);
-      }
-#endif
       // stores grouped so that each lane class takes one exec-mask region
       if (valid && ((wid == 0 && rg == 0) || !piv)) {
         double* wl = WL + r * kWLs;
@@ -2000,15 +1957,9 @@ __global__ __launch_bounds__(kBlkWG) __attribute__((amdgpu_waves_per_eu(2))) voi
       }
       if (wid == 0 && lane == 0 && bad) *fail_p = 1;
     }
-#ifdef SLAM_SOLVE_PROFILE_STEP
-    const uint64_t q2 = __builtin_amdgcn_s_memtime();
-#endif
     SOLVE_TR(c0 / kPanelW, 2);
     __syncthreads();
     SOLVE_TR(c0 / kPanelW, 3);
-#ifdef SLAM_SOLVE_PROFILE_STEP
-    const uint64_t q3 = __builtin_amdgcn_s_memtime();
-#endif
     if (*fail_p) {
       ok = false;
       break;
@@ -2043,18 +1994,6 @@ __global__ __launch_bounds__(kBlkWG) __attribute__((amdgpu_waves_per_eu(2))) voi
       acc[0][0] = chk;
     }
     SOLVE_TR(c0 / kPanelW, 4);
-#endif
-#ifdef SLAM_SOLVE_PROFILE_STEP
-    __builtin_amdgcn_s_waitcnt(0);
-    const uint64_t q4 = __builtin_amdgcn_s_memtime();
-    if (t == 0 && c0 == 9 * (n / 18)) {
-      p.state[12] = (double)(q1 - q0);
-      p.state[13] = (double)(q2 - q1);
-#ifndef SLAM_SOLVE_PROFILE_PANEL
-      p.state[14] = (double)(q3 - q2);
-      p.state[15] = (double)(q4 - q3);
-#endif
-    }
 #endif
   }
   SOLVE_PROF_T(2);
@@ -2132,9 +2071,6 @@ __global__ __launch_bounds__(kBlkWG) __attribute__((amdgpu_waves_per_eu(2))) voi
 // end in solve_epilogue.  The diagonal-tile factor + inverse is
 // tile_chol_inv_blk (16x16 diagonal blocks in wave 0's registers, the rest on
 // the f64 matrix cores).
-#ifndef SLAM_TL_KSKIP
-#define SLAM_TL_KSKIP 0    // 1: the flow kernel's products skip a tile's padding k-blocks
-#endif
 #ifndef SLAM_TL_PADSKIP
 #define SLAM_TL_PADSKIP 1  // the tile factor skips the pivot chain of padding blocks
 #endif
@@ -2156,7 +2092,7 @@ struct TlLayout {  // doubles inside p.chol; T = the schedule's tile count (ba.t
     x = y + N;
     nz = x + N;                          // T*T bytes
     fail = nz + ((long long)T * T + 7) / 8;
-    xo = fail + 8;                       // fail flag + 7 profiling slots (SLAM_TL_PROFILE)
+    xo = fail + 8;                       // fail flag + 7 spare slots (ba.py mirrors this layout)
     fc = xo + N;                         // k_tl3_flow: x in camera order; [T][T][64] L_Ik y_k
     epi = fc + (long long)T * T * kTB;   // (forward-substitution terms); [T][2] epilogue partials
     flow = epi + 2 * T;                  // (pc, cost per tile), then ints: flags
@@ -2226,11 +2162,8 @@ __device__ __forceinline__ int frag_swz(int r, int c) {
   const int F = ((r >> 4) << 4) + (c >> 2), hi = c & 3;
   return (F << 6) + (hi << 4) + (((r & 15) + 4 * hi + (F & 3)) & 15);
 }
-// gemm_xyT_lowY with both operands in frag_swz order (same products, same order);
-// only the k-steps kk < kmax (Y's columns past a tile's camera rows are padding:
-// X's entries there are exact zeros)
-__device__ __forceinline__ void gemm_xyT_lowY_swz(const double* Xf, const double* Yf, d4 acc[4],
-                                                  int kmax = 16) {
+// gemm_xyT_lowY with both operands in frag_swz order (same products, same order)
+__device__ __forceinline__ void gemm_xyT_lowY_swz(const double* Xf, const double* Yf, d4 acc[4]) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   int so[4];
 #pragma unroll
@@ -2239,7 +2172,6 @@ __device__ __forceinline__ void gemm_xyT_lowY_swz(const double* Xf, const double
   for (int s = 0; s < 4; ++s) acc[s] = d4{0.0, 0.0, 0.0, 0.0};
   static_for<0, 16>([&](auto K) {
     constexpr int kk = decltype(K)::value;
-    if (SLAM_TL_KSKIP && kk >= kmax) return;  // (uniform)
     const double a = Xf[((w * 16 + kk) << 6) + so[kk & 3]];
     static_for<kk / 4, 4>([&](auto S) {
       constexpr int s = decltype(S)::value;
@@ -2311,15 +2243,8 @@ __device__ __forceinline__ d4 ld16(const double* C, int sc) {
   return acc;
 }
 
-#ifdef SLAM_TL_PROFILE
-__device__ unsigned long long g_tl_stamp[8];
-#define TL_STAMP(i) \
-  if (blockIdx.x == 1 && threadIdx.x == 0 && tl_prof_on) g_tl_stamp[i] = wall_clock64()
-#else
-#define TL_STAMP(i) (void)0
-#endif
-// Akk == nullptr: the tile is already in M (written before the call; the
-// first barrier below publishes it).
+// -DSLAM_FLOW_PROFILE: wall clock at the steps of workgroup 0's tile factor
+// (slam_flow_fac_stamps, scripts/flow_prof.py)
 #ifdef SLAM_FLOW_PROFILE
 __device__ unsigned long long g_flow_fac[16];
 #define FAC_T(i)                                                    \
@@ -2637,11 +2562,12 @@ __device__ __forceinline__ void blk_identity_w0(double* Xb, int p) {
   }
 }
 
+// The tile factor (described above kMS).  Akk == nullptr: the tile is already
+// in M (written before the call; the first barrier below publishes it).
 __device__ __forceinline__ bool tile_chol_inv_blk(const double* __restrict__ Akk, int ld,
                                                   double* M, double* Xb, double* Tb, int* okp,
-                                                  int nb = 4, bool tl_prof_on = false) {
+                                                  int nb = 4) {
   const int t = threadIdx.x, l = t & 63, w = t >> 6;
-  TL_STAMP(0);
   if (Akk != nullptr) {
     // all 16 loads of a lane in flight before the LDS stores
     double tmp[kTB * kTB / kTlWG];
@@ -2665,7 +2591,6 @@ __device__ __forceinline__ bool tile_chol_inv_blk(const double* __restrict__ Akk
   int* fl = reinterpret_cast<int*>(Tb + 3 * 16 * kBS17);
   if (t < 6) fl[t] = 0;
   __syncthreads();
-  TL_STAMP(1);
   FAC_T(0);
   // One loop over the block columns with ONE instance of wave 0's 16x16 code
   // (an instance per block column measured 0.4-1.0 us slower per block: the
@@ -2775,10 +2700,8 @@ __device__ __forceinline__ bool tile_chol_inv_blk(const double* __restrict__ Akk
   FAC_T(12);
   __syncthreads();  // X_33 published
   if (w > 0) X_from(3, w == 1 ? 1 : (w == 2 ? 0 : 2), T3);
-  TL_STAMP(2);
   if (w == 0 && l == 0) *okp = ok ? 1 : 0;
   __syncthreads();
-  TL_STAMP(3);
   FAC_T(13);
   return *okp != 0;
 }
@@ -3152,12 +3075,13 @@ __device__ __forceinline__ int flow_fcode(const int* fail, int epoch) {
 }
 __device__ __forceinline__ void flow_fail(int* fail, int epoch, int code) { st_flag(fail, (epoch << 2) | code); }
 
-// Thread 0 polls until *flag == epoch; false (uniform) when the solve failed or
+// Thread 0 polls until up() holds; false (uniform) when the solve failed or
 // the wait timed out (which marks it failed).
-__device__ bool flow_wait(const int* flag, int epoch, int* fail, int* sh) {
+template <typename Up>
+__device__ __forceinline__ bool flow_poll(Up up, int epoch, int* fail, int* sh) {
   if (threadIdx.x == 0) {
     int ok = 1;
-    for (int spins = 0; ld_flag(flag) != epoch; ++spins) {
+    for (int spins = 0; !up(); ++spins) {
       if (flow_fcode(fail, epoch) != 0) {
         ok = 0;
         break;
@@ -3175,6 +3099,16 @@ __device__ bool flow_wait(const int* flag, int epoch, int* fail, int* sh) {
   const bool ok = *sh != 0;
   __syncthreads();
   return ok;
+}
+// ... until *flag == epoch
+__device__ bool flow_wait(const int* flag, int epoch, int* fail, int* sh) {
+  return flow_poll([=] { return ld_flag(flag) == epoch; }, epoch, fail, sh);
+}
+// ... until the low half (retired row tiles) of column J's parent counter
+// reaches rc -- the retirers' x stores drained before their adds (the counter
+// is the acquire for those bytes)
+__device__ bool flow_wait_count(const int* cnt, int rc, int epoch, int* fail, int* sh) {
+  return flow_poll([=] { return (ld_flag(cnt) & 0xffff) >= rc; }, epoch, fail, sh);
 }
 
 // Wave 0 polls base[idx[i]] == epoch for all i < cnt together (lane i, chunks
@@ -3202,39 +3136,6 @@ __device__ bool flow_wait_many(const int* base, const int32_t* idx, int cnt, int
       }
     }
     if (lane == 0) *sh = ok;
-  }
-  __syncthreads();
-  const bool ok = *sh != 0;
-  __syncthreads();
-  return ok;
-}
-
-// one flag, the same contract as flow_wait (its definition follows below)
-__device__ bool flow_wait(const int* flag, int epoch, int* fail, int* sh);
-__device__ __forceinline__ bool flow_wait_one(const int* flag, int epoch, int* fail, int* sh) {
-  return flow_wait(flag, epoch, fail, sh);
-}
-
-// Thread 0 polls the parent counter of column J until its low half (retired row
-// tiles) reaches rc -- the retirers' x stores drained before their adds (the
-// counter is the acquire for those bytes); false (uniform) when the solve failed
-// or the wait timed out.
-__device__ bool flow_wait_count(const int* cnt, int rc, int epoch, int* fail, int* sh) {
-  if (threadIdx.x == 0) {
-    int ok = 1;
-    for (int spins = 0; (ld_flag(cnt) & 0xffff) < rc; ++spins) {
-      if (flow_fcode(fail, epoch) != 0) {
-        ok = 0;
-        break;
-      }
-      if (spins > kFlowSpinMax) {
-        flow_fail(fail, epoch, 2);
-        ok = 0;
-        break;
-      }
-      __builtin_amdgcn_s_sleep(SLAM_FLOW_SLEEP);
-    }
-    *sh = ok;
   }
   __syncthreads();
   const bool ok = *sh != 0;
@@ -3283,28 +3184,15 @@ __device__ __forceinline__ void tiles2_to_frag_sc1(const double* __restrict__ g0
   }
 }
 
-// acc[s] += (rows 16w.., cols 16s.. of X Y^T), X and Y in fragment order, over
-// the first nbk 16-column blocks of k (the columns of a child tile past its
-// camera rows' blocks are exact zeros in both operands)
-__device__ __forceinline__ void gemm_xyT_acc(const double* Xf, const double* Yf, d4 acc[4],
-                                             int nbk = 4) {
+// acc[s] += (rows 16w.., cols 16s.. of X Y^T), X and Y in fragment order
+__device__ __forceinline__ void gemm_xyT_acc(const double* Xf, const double* Yf, d4 acc[4]) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#if SLAM_TL_KSKIP
-  for (int kb = 0; kb < nbk; ++kb) {
-#pragma unroll
-    for (int k4 = 0; k4 < 4; ++k4) {
-      const int kk = 4 * kb + k4;
-#else
-  (void)nbk;
-  {
 #pragma unroll 4
-    for (int kk = 0; kk < 16; ++kk) {
-#endif
-      const double a = Xf[((w * 16 + kk) << 6) + lane];
+  for (int kk = 0; kk < 16; ++kk) {
+    const double a = Xf[((w * 16 + kk) << 6) + lane];
 #pragma unroll
-      for (int s = 0; s < 4; ++s)
-        acc[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Yf[((s * 16 + kk) << 6) + lane], acc[s], 0, 0, 0);
-    }
+    for (int s = 0; s < 4; ++s)
+      acc[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Yf[((s * 16 + kk) << 6) + lane], acc[s], 0, 0, 0);
   }
 }
 
@@ -3376,11 +3264,9 @@ void k_tl3_flow(slam_ba_problem p, int T_) {
   const int epoch = ep_sh;
   const int32_t* rec = S + S[5] + 5 * J;
   const int ro = rec[0], rc = rec[1], so = rec[2], sc = rec[3], uo = rec[4];
-  // rows of a tile (its rows of S first, padding after them): the 16-row
-  // blocks of the factor and of the products over its columns
-  const int32_t* trows = tl_tile_rows(S, n, T);
-  auto nblk = [&](int k) { return (trows[k] + 15) >> 4; };
-  const int nbJ = nblk(J);
+  // rows of the tile (its rows of S first, padding after them): the 16-row
+  // blocks of the factor
+  const int nbJ = (tl_tile_rows(S, n, T)[J] + 15) >> 4;
   // Product tasks (ba.tl_schedule): the terms L_Ik L_Jk^T of a column J's rows
   // 0 and 1 are formed by column k itself, as soon as both of its tiles exist,
   // into slots that J sums after its factor -- J's diagonal phase never waits
@@ -3490,25 +3376,12 @@ void k_tl3_flow(slam_ba_problem p, int T_) {
       __syncthreads();
       if (pre) tile_to_frag_sc1(A + (size_t)J * kTB * L.N + S[so + q + 1] * kTB, L.N, nxt);
     }
-#if SLAM_TL_KSKIP
-    const int kmk = nblk(S[so + q]);  // child k's column blocks past its rows: zeros
-    for (int kb = 0; kb < kmk; ++kb)
-#pragma unroll
-      for (int k4 = 0; k4 < 4; ++k4)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) {
-          const int kk = 4 * kb + k4;
-          acc[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[((dR[b] * 16 + kk) << 6) + lane],
-                                                        cur[((dC[b] * 16 + kk) << 6) + lane], acc[b], 0, 0, 0);
-        }
-#else
 #pragma unroll 4
     for (int kk = 0; kk < 16; ++kk)
 #pragma unroll
       for (int b = 0; b < 3; ++b)
         acc[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[((dR[b] * 16 + kk) << 6) + lane],
                                                       cur[((dC[b] * 16 + kk) << 6) + lane], acc[b], 0, 0, 0);
-#endif
     if (q + 1 < sc) {
       if (!pre) {
         ok = flow_wait(F.tile + J * T + S[so + q + 1], epoch, fail, &shf);
@@ -3603,7 +3476,7 @@ void k_tl3_flow(slam_ba_problem p, int T_) {
         tiles2_to_frag_sc1(A + (size_t)I * kTB * L.N + k * kTB, A + (size_t)J * kTB * L.N + k * kTB, L.N,
                            Yf, Xf);
         __syncthreads();
-        gemm_xyT_acc(Yf, Xf, acc, nblk(k));
+        gemm_xyT_acc(Yf, Xf, acc);
         __syncthreads();
       }
     }
@@ -3635,7 +3508,7 @@ void k_tl3_flow(slam_ba_problem p, int T_) {
     __syncthreads();
     if (q == 0) FLOW_S(3);
     d4 lacc[4];
-    gemm_xyT_lowY_swz(stg, Vf, lacc, 4 * nbJ);  // L_IJ = A_IJ (L_JJ^-1)^T
+    gemm_xyT_lowY_swz(stg, Vf, lacc);  // L_IJ = A_IJ (L_JJ^-1)^T
 #ifdef SLAM_FLOW_PROFILE
     if (q == 0) {
       __builtin_amdgcn_s_waitcnt(0);
@@ -3685,7 +3558,7 @@ void k_tl3_flow(slam_ba_problem p, int T_) {
       d4 pacc[4];
 #pragma unroll
       for (int s2 = 0; s2 < 4; ++s2) pacc[s2] = d4{0.0, 0.0, 0.0, 0.0};
-      gemm_xyT_acc(Xf, Yf, pacc, nbJ);
+      gemm_xyT_acc(Xf, Yf, pacc);
       double* Cp = prod + (size_t)slot * kTB * kTB;
 #pragma unroll
       for (int s2 = 0; s2 < 4; ++s2)
@@ -3801,7 +3674,7 @@ void k_tl3_flow(slam_ba_problem p, int T_) {
       __syncthreads();
       k = cur_sh;
       if (k < 0) break;
-      okk = flow_wait_one(F.dv + k, epoch, fail, &shf);
+      okk = flow_wait(F.dv + k, epoch, fail, &shf);
     }
     const bool own = k == J;
     const int32_t* rk = S + S[5] + 5 * k;
@@ -4497,14 +4370,6 @@ extern "C" int slam_flow_fac_stamps(unsigned long long* out16) {
 extern "C" int slam_flow_stamps(unsigned long long* out, int n_cols) {
   SLAM_HIP(hipDeviceSynchronize());
   SLAM_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_flow_stamp), (size_t)n_cols * 8 * sizeof(unsigned long long)));
-  return SLAM_OK;
-}
-#endif
-
-#ifdef SLAM_TL_PROFILE
-extern "C" int slam_tl_stamps(unsigned long long* out8) {
-  SLAM_HIP(hipDeviceSynchronize());
-  SLAM_HIP(hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_tl_stamp), 8 * sizeof(unsigned long long)));
   return SLAM_OK;
 }
 #endif
