@@ -307,8 +307,8 @@ int slam_ba_jacobian(const double* d_cams, const double* d_pts, const int32_t* d
 /* LM state slots (doubles in slam_ba_problem.state). */
 #define SLAM_BA_ST_LAMBDA 0
 #define SLAM_BA_ST_NU 1
-#define SLAM_BA_ST_COST 2      /* 0.5*|r|^2 at the live parameters           */
-#define SLAM_BA_ST_COST_NEW 3  /* 0.5*|r|^2 at the last trial step            */
+#define SLAM_BA_ST_COST 2      /* 0.5*|r|^2 at the live parameters (with a robust  */
+#define SLAM_BA_ST_COST_NEW 3  /* loss: 0.5 d^2 sum rho(z)); at the last trial step */
 #define SLAM_BA_ST_PRED 4      /* predicted reduction of the last trial step   */
 #define SLAM_BA_ST_RHO 5
 #define SLAM_BA_ST_ACCEPTED 6  /* 1 if the last trial step was accepted        */
@@ -420,7 +420,18 @@ typedef struct slam_ba_problem {
    * asm_tab only; n_asm_act >= 1. */
   const int32_t* asm_act;
   int32_t n_asm_act;
-  int32_t asm_pad;
+  /* Robust loss per observation (was the unused asm_pad; 0 keeps the plain
+   * 0.5 |r|^2): 0 linear, 1 huber, 2 soft_l1, 3 cauchy -- scipy's names and
+   * rho, applied to the 2-vector reprojection error.  With s = r0^2 + r1^2 of
+   * the clamped residual and z = s / loss_scale^2 the observation enters the
+   * normal equations as sqrt(w) r and sqrt(w) J (all 12 columns), w = rho'(z)
+   * (the Gauss-Newton / IRLS form, no rho'' term), and the LM cost is
+   * 0.5 loss_scale^2 sum rho(z) (SLAM_BA_ST_COST / _COST_NEW).  huber: rho =
+   * z (z <= 1) or 2 sqrt(z) - 1; soft_l1: 2 (sqrt(1 + z) - 1); cauchy:
+   * log(1 + z).  The launchers refuse loss outside 0..3 and, with loss != 0,
+   * a loss_scale that is not finite and > 0.  Landmark shards: every rank
+   * passes the same loss.  slam_ba_residual / slam_ba_jacobian stay raw. */
+  int32_t loss;
   /* Optional (null: every parameter free): held camera parameters, one word
    * per camera [n_cams]; bit i (0..8: w0 w1 w2 t0 t1 t2 f k1 k2) set holds
    * parameter i of that camera constant -- its column leaves the Jacobian
@@ -432,9 +443,10 @@ typedef struct slam_ba_problem {
    * passes the same words.  Appended in ABI 1 (slam_abi_version() still
    * returns 1): callers that zero the descriptor keep today's behaviour, and
    * slam_ba_problem_size() tells a binding which layout a library has. */
-  const uint32_t* cam_fixed;
+  double loss_scale;            /* delta of `loss` in pixels (read when loss != 0) */
+  const uint32_t* cam_fixed;    /* (documented above loss_scale; stays the last field) */
 } slam_ba_problem;
-/* sizeof(slam_ba_problem) of this library (400 with cam_fixed). */
+/* sizeof(slam_ba_problem) of this library (400 with cam_fixed, 408 with loss_scale). */
 int slam_ba_problem_size(void);
 
 /* Largest tile count (tl_sched[1]) the dataflow tiled solve takes: one
@@ -442,7 +454,7 @@ int slam_ba_problem_size(void);
 #define SLAM_TL_FLOW_MAX_T 256
 
 /* Problems per batched launch (slam_ba_iterate_batch splits larger batches).
- * The descriptors travel by value in the kernel arguments: 16 x 400 B
+ * The descriptors travel by value in the kernel arguments: 16 x 408 B
  * (ba.hip static_asserts the size; ROCm 7.2 takes this > 4 KB argument
  * segment, exercised by tests/test_ba.py's 16-window launch). */
 #ifndef SLAM_BA_MAX_BATCH

@@ -54,7 +54,7 @@ constexpr int kBS = 256;   // block size of the element-wise kernels
 // Batched LM: independent problems (local-BA windows) advance through one set
 // of launches, one problem per blockIdx.y; each keeps its own buffers and LM
 // state, so the iterates of a batched problem equal its solo iterates.  The
-// problem descriptors travel by value in the kernel arguments (16 x 400 B).
+// problem descriptors travel by value in the kernel arguments (16 x 408 B).
 constexpr int kBaMaxBatch = SLAM_BA_MAX_BATCH;
 struct BaBatch {
   slam_ba_problem p[kBaMaxBatch];
@@ -82,10 +82,10 @@ __device__ __forceinline__ int2 ba_xcd_map() {
   const int2 bw_ = ba_xcd_map();     \
   const int bx = bw_.x;              \
   const slam_ba_problem& p = (b).p[bw_.y]
-// the batch travels by value in the kernel arguments: 16 x 400 B,
+// the batch travels by value in the kernel arguments: 16 x 408 B,
 // beyond the traditional 4 KB; ROCm 7.2 takes it (tests/test_ba.py launches 16)
-static_assert(sizeof(slam_ba_problem) == 400, "slam_ba_problem grew: re-check the kernarg size");
-static_assert(sizeof(BaBatch) <= 16 * 400, "BaBatch kernel argument size");
+static_assert(sizeof(slam_ba_problem) == 408, "slam_ba_problem grew: re-check the kernarg size");
+static_assert(sizeof(BaBatch) <= 16 * 408, "BaBatch kernel argument size");
 
 // The LM kernels are short and latency-bound and usually share their CUs with
 // the (throughput-bound) ORB workgroups of the concurrent tracking stream: they
@@ -263,6 +263,44 @@ __device__ __forceinline__ void hold_cols_half(double Jh[2][6], unsigned fx) {
 #pragma unroll
   for (int i = 0; i < (H == 0 ? 6 : 3); ++i)
     if ((fx >> (6 * H + i)) & 1u) Jh[0][i] = Jh[1][i] = 0.0;
+}
+
+// Robust loss per observation (slam_ba_problem.loss != 0, delta = loss_scale):
+// with s = |r|^2 of the clamped residual and z = s / delta^2, r and the lane's
+// NC Jacobian columns (J0, J1: rows 0, 1; 12, a half's 6, or 0 = none) are
+// scaled by sqrt(w), w = rho'(z), and delta^2 rho(z) is returned -- the
+// observation's term of twice the LM cost, in place of s.  Both lanes of a
+// split observation hold the full r, so both form the same w.  After the clamp
+// and hold_cols (a held column is 0 and stays 0).  huber with z <= 1 is the
+// plain loss exactly: nothing is scaled, s is returned.
+template <int NC>
+__device__ __forceinline__ double robust_weight(double r[2], double* J0, double* J1, int loss,
+                                                double delta) {
+  const double s = r[0] * r[0] + r[1] * r[1];
+  const double d2 = delta * delta;
+  const double z = s / d2;
+  double sw, rho;
+  if (loss == 1) {         // huber: rho = z | 2 sqrt(z) - 1, w = 1 | 1 / sqrt(z)
+    if (z <= 1.0) return s;
+    const double q = sqrt(z);
+    sw = 1.0 / sqrt(q);
+    rho = 2.0 * q - 1.0;
+  } else if (loss == 2) {  // soft_l1: rho = 2 (sqrt(1 + z) - 1), w = 1 / sqrt(1 + z)
+    const double q = sqrt(1.0 + z);
+    sw = 1.0 / sqrt(q);
+    rho = 2.0 * z / (q + 1.0);  // = 2 (q - 1) without the cancellation at small z
+  } else {                 // cauchy: rho = log(1 + z), w = 1 / (1 + z)
+    sw = 1.0 / sqrt(1.0 + z);
+    rho = log1p(z);
+  }
+  r[0] *= sw;
+  r[1] *= sw;
+#pragma unroll
+  for (int k = 0; k < NC; ++k) {
+    J0[k] *= sw;
+    J1[k] *= sw;
+  }
+  return d2 * rho;
 }
 
 // reproject_pre<true> + clamp_rows<true> split over two lanes by Jacobian
@@ -493,7 +531,7 @@ constexpr int kLinWG = 256;  // k_linearize: obs / point phases use kGrp lanes, 
 constexpr int kSlotLds = 128;  // slot ranges staged in LDS (larger groups read them from memory)
 constexpr int kPairLds = 1024; // observation pairs staged in LDS (ditto)
 
-// LDS of k_linearize (64.5 KiB: leaves room for a co-resident ORB workgroup)
+// LDS of k_linearize (65.5 KiB: leaves room for a co-resident ORB workgroup)
 struct LinLds {
   double jc[kGrp][18];  // Jc rows (2 x 9)
   double w[kGrp][27];   // W = Jc^T Jp [i][c]; before phase 3: Jp (6), r (2)
@@ -505,6 +543,7 @@ struct LinLds {
   int bptr[kSlotLds];   // block-slot ranges in pairs
   int pairs[kPairLds];  // the group's observation pairs (when <= kPairLds)
   unsigned fx[kGrp];    // held-parameter mask of each observation's camera (cam_fixed only)
+  double rho[kGrp];     // delta^2 rho(z) of each observation (robust loss only)
 };
 
 // Y_o row i (= W_o row i times V*^-1, V*^-1 symmetric) of a group observation
@@ -533,11 +572,13 @@ __device__ __forceinline__ void y_row(const double* W, const double* Vi, int i, 
 // (405 lanes' worth at C3: two rounds of the workgroup).
 // cptr / bptr: slot ranges (minus coff / boff) into the group's camera-slot
 // observations (L.cobs) and observation pairs.
+template <bool ROBUST>
 __device__ __forceinline__ void lin_slots(const slam_ba_problem& p, LinLds& L, int cs0, int ncs,
                                           int bs0, int nbs, const int* cptr, int coff,
                                           const int* bptr, int boff, const int* pairs) {
   const int t = threadIdx.x;
   const int* cobs = L.cobs;
+  const bool robust = ROBUST && p.loss != 0;  // uniform: the cost term is delta^2 rho(z) (L.rho), not |r~|^2
   for (int item = t; item < 9 * (ncs + nbs); item += kLinWG) {
     const int sl = item / 9, i = item - 9 * sl;
     double acc[9];
@@ -567,7 +608,8 @@ __device__ __forceinline__ void lin_slots(const slam_ba_problem& p, LinLds& L, i
         vr = __builtin_fma(a0, r0, __builtin_fma(a1, r1, vr));
         vu = __builtin_fma(a0, L.ru[k][2], __builtin_fma(a1, L.ru[k][3], vu));
         vd = __builtin_fma(a0, a0, __builtin_fma(a1, a1, vd));
-        cost = __builtin_fma(r0, r0, __builtin_fma(r1, r1, cost));
+        if (robust) cost += L.rho[k];
+        else cost = __builtin_fma(r0, r0, __builtin_fma(r1, r1, cost));
         k = kn;
         lk = lkn;
       }
@@ -601,6 +643,7 @@ __device__ __forceinline__ void lin_slots(const slam_ba_problem& p, LinLds& L, i
   }
 }
 
+template <bool ROBUST>  // as k_lin_mfma
 __global__ __launch_bounds__(kLinWG) void k_linearize(BaBatch bat) {
   BA_PROB_X(bat);
   const int g = bx;
@@ -663,6 +706,23 @@ __global__ __launch_bounds__(kLinWG) void k_linearize(BaBatch bat) {
       }
     }
   }
+  if (ROBUST && p.loss != 0) {
+    // robust loss: r and all 12 columns scaled by sqrt(w), in the registers (W
+    // below) and in the LDS rows the point and slot phases read
+    if (has) {
+      L.rho[t] = robust_weight<12>(r, J[0], J[1], p.loss, p.loss_scale);
+#pragma unroll
+      for (int a = 0; a < 2; ++a) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) L.jc[t][9 * a + i] = J[a][i];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) L.w[t][3 * a + c] = J[a][9 + c];
+        L.w[t][6 + a] = r[a];
+        L.ru[t][a] = r[a];
+      }
+    }
+    __syncthreads();
+  }
   const double lam = p.state[SLAM_BA_ST_LAMBDA];
   if (t < p1 - p0) {
     const int pt = p0 + t;
@@ -692,10 +752,10 @@ __global__ __launch_bounds__(kLinWG) void k_linearize(BaBatch bat) {
   // slot phase: LDS-staged lists when they fit (always at C3), else from memory
   // (two inlined copies, so every list access is a plain ds_read or global load)
   if (fit_c && fit_b && fit_p)
-    lin_slots(p, L, cs0, ncs, bs0, nbs, L.cptr, 0, L.bptr, 0, L.pairs);
+    lin_slots<ROBUST>(p, L, cs0, ncs, bs0, nbs, L.cptr, 0, L.bptr, 0, L.pairs);
   else
-    lin_slots(p, L, cs0, ncs, bs0, nbs, p.cslot_obs_ptr + cs0, cb0, p.bslot_pair_ptr + bs0, pb0,
-              p.bslot_pairs + pb0);
+    lin_slots<ROBUST>(p, L, cs0, ncs, bs0, nbs, p.cslot_obs_ptr + cs0, cb0, p.bslot_pair_ptr + bs0, pb0,
+                      p.bslot_pairs + pb0);
 }
 
 // ---------------------------------------------------------------- camera-union linearisation
@@ -876,6 +936,7 @@ __device__ void rows_sum(const double* __restrict__ part, int stride, int rb, in
 // (sc1 loads, 4 in flight, the parts n apart in red).  The write-out after the
 // sums repeats k_assemble's statement for statement: as one shared function it
 // changed both kernels' instructions (profiles/ba_dead_knobs/README.md).
+template <bool ROBUST>  // the calling k_lin_mfma's: see lin_fold_assemble
 __device__ void fold_block(const slam_ba_problem& p, int blk, double* scratch) {
   double* red = scratch;             // [<= 3][112]
   double* sh = scratch + 3 * kCPart;  // [112]
@@ -919,6 +980,7 @@ __device__ void fold_block(const slam_ba_problem& p, int blk, double* scratch) {
 
 // a block with no partial row in this problem: zeros (and zero vectors when
 // diagonal), every build -- the packed multi-rank sys is all-reduced in place
+template <bool ROBUST>  // the calling k_lin_mfma's: see lin_fold_assemble
 __device__ void fold_zero_block(const slam_ba_problem& p, int blk, int t0, int nt) {
   const int c1 = p.blocks[2 * blk], c2 = p.blocks[2 * blk + 1];
   const int C9 = 9 * p.n_cams;
@@ -940,6 +1002,11 @@ __device__ void fold_zero_block(const slam_ba_problem& p, int blk, int t0, int n
     }
 }
 
+// ROBUST (here, in fold_block and in fold_zero_block): the calling k_lin_mfma's,
+// nothing else -- each of its two instantiations gets its own copy of these
+// functions (one caller each, inlined as before the kernel was a template)
+// and its own `done` / `ndone` in LDS.
+template <bool ROBUST>
 __device__ void lin_fold_assemble(const slam_ba_problem& p, const int* cams, int m, int nb,
                                   const int* brow, double* scratch) {
   const AsmTab A(p);
@@ -960,7 +1027,7 @@ __device__ void lin_fold_assemble(const slam_ba_problem& p, const int* cams, int
     ndone = n;
   }
   __syncthreads();
-  for (int q = 0; q < ndone; ++q) fold_block(p, done[q], scratch);
+  for (int q = 0; q < ndone; ++q) fold_block<ROBUST>(p, done[q], scratch);
 }
 
 // The deal of (D)'s accumulation units -- the 10 upper 16x16 tiles of T (12
@@ -1070,6 +1137,11 @@ __device__ __forceinline__ void linm_cams(const MLds& L, d4 (&u)[5], const int (
   }
 }
 
+// ROBUST: the instantiation that can weigh observations by a robust loss,
+// launched when a problem of the batch has loss != 0 (each problem then
+// branches on its own loss); in the other one the loss steps are compiled
+// out: the plain path runs the code it ran before the loss existed.
+template <bool ROBUST>
 __global__ __launch_bounds__(kMWG) void k_lin_mfma(BaBatch bat) {
   BA_PROB_X(bat);
   const int sg = bx;
@@ -1079,7 +1151,7 @@ __global__ __launch_bounds__(kMWG) void k_lin_mfma(BaBatch bat) {
   __shared__ MLds L;
   if (p.asm_tab != nullptr) {  // folded assembly: this supergroup's share of the empty blocks
     const AsmTab A(p);
-    for (int q = sg; q < A.n_empty; q += p.n_sgrps) fold_zero_block(p, A.empty[q], threadIdx.x, kMWG);
+    for (int q = sg; q < A.n_empty; q += p.n_sgrps) fold_zero_block<ROBUST>(p, A.empty[q], threadIdx.x, kMWG);
   }
   const int t = threadIdx.x, lane = t & 63;
   const int wid = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -1091,6 +1163,13 @@ __global__ __launch_bounds__(kMWG) void k_lin_mfma(BaBatch bat) {
   const int cur = cur_of(p.state);
   const double lam = p.state[SLAM_BA_ST_LAMBDA];
   const bool held = p.cam_fixed != nullptr;  // uniform: without a mask (A) takes no extra step
+  // robust loss (uniform: the plain loss takes no extra step): (A) scales r and
+  // J by sqrt(w), so the camera tile's entry (9, 9) is sum |r~|^2, not the
+  // cost; each observation's first-half lane sums its delta^2 rho(z) over the
+  // chunks in rcost, reduced in a fixed order in (E) and booked on the
+  // supergroup's first camera row (only the sum over the rows is consumed)
+  const bool robust = ROBUST && p.loss != 0;
+  double rcost = 0.0;
   // the supergroup's camera records -> LDS (one load per lane)
   if (t < kMCams * kCamRec) {
     const int a = t / kCamRec, k = t - kCamRec * (t / kCamRec);
@@ -1218,6 +1297,7 @@ __global__ __launch_bounds__(kMWG) void k_lin_mfma(BaBatch bat) {
         if (t < 128) {
           reproject_half<0>(L.cam[L.la[k]], L.X[L.lpt[k]], q, r, Jh);
           if (held) hold_cols_half<0>(Jh, L.fx[L.la[k]]);
+          if (robust) rcost += robust_weight<6>(r, Jh[0], Jh[1], p.loss, p.loss_scale);
 #pragma unroll
           for (int a = 0; a < 2; ++a) {
 #pragma unroll
@@ -1227,6 +1307,7 @@ __global__ __launch_bounds__(kMWG) void k_lin_mfma(BaBatch bat) {
         } else {
           reproject_half<1>(L.cam[L.la[k]], L.X[L.lpt[k]], q, r, Jh);
           if (held) hold_cols_half<1>(Jh, L.fx[L.la[k]]);
+          if (robust) robust_weight<6>(r, Jh[0], Jh[1], p.loss, p.loss_scale);
 #pragma unroll
           for (int a = 0; a < 2; ++a) {
 #pragma unroll
@@ -1368,6 +1449,11 @@ __global__ __launch_bounds__(kMWG) void k_lin_mfma(BaBatch bat) {
   }
   // (E) T and the Z_a tiles -> LDS staging (aliases the operand planes), then
   //     the partial rows
+  double* rsum = &L.e[0][0];  // robust: the waves' delta^2 rho sums ((C) of the last chunk is done with e)
+  if (robust) {
+    for (int off = 32; off > 0; off >>= 1) rcost += __shfl_down(rcost, off, 64);  // fixed tree
+    if (lane == 0) rsum[wid] = rcost;  // waves 2, 3: the second-half lanes hold 0
+  }
   __syncthreads();
   double* T = &L.yt[0][0][0];
   double* Z = T + kMRows * kMRows;  // [kMCams][16][16]
@@ -1405,6 +1491,7 @@ __global__ __launch_bounds__(kMWG) void k_lin_mfma(BaBatch bat) {
       v = Za[(e - 99) * 17];       // diag U
     } else {
       v = Za[9 * 16 + 9];          // |r|^2
+      if (robust) v = a == 0 ? rsum[0] + rsum[1] : 0.0;  // sum delta^2 rho(z), on the first row
     }
     // written through (sc1) only for the folded assembly (other CUs read them in
     // this launch); plain stores keep the lines in L2 for k_assemble
@@ -1422,7 +1509,7 @@ __global__ __launch_bounds__(kMWG) void k_lin_mfma(BaBatch bat) {
     else *bp = v;
   }
   LINM_T(6);
-  if (p.asm_tab != nullptr) lin_fold_assemble(p, sm + 10, m, nb, L.brow, &L.jc[0][0]);
+  if (p.asm_tab != nullptr) lin_fold_assemble<ROBUST>(p, sm + 10, m, nb, L.brow, &L.jc[0][0]);
   LINM_END();
 }
 
@@ -3923,7 +4010,7 @@ __device__ void lm_decide(double* __restrict__ state, const double* __restrict__
 // stores; the last workgroup to finish (agent-scope ticket) sums them in a
 // fixed order into small[0..1] and, when DECIDE (single rank), applies the LM
 // decision.
-template <bool DECIDE>
+template <bool DECIDE, bool ROBUST>  // ROBUST as k_lin_mfma
 __global__ __launch_bounds__(kGrp) void k_back_trial(BaBatch bat) {
   BA_PROB_X(bat);
   const int g = bx, G = p.n_grps;
@@ -3958,6 +4045,9 @@ __global__ __launch_bounds__(kGrp) void k_back_trial(BaBatch bat) {
     reproject_pre<true>(p.camrec[cur] + kCamRec * p.obs_cam[o], p.pts[cur] + 3 * pt,
                         p.obs_q + 2 * o, r, J);
     clamp_rows<true>(r, J);
+    // the lineariser's weights (a held column only ever multiplies its zero
+    // step below, so hold_cols is not repeated here)
+    if (ROBUST && p.loss != 0) robust_weight<12>(r, J[0], J[1], p.loss, p.loss_scale);
     const double* dc = p.delta_c + 9 * p.obs_cam[o];
     double w0 = 0.0, w1 = 0.0, w2 = 0.0;
 #pragma unroll
@@ -4012,7 +4102,8 @@ __global__ __launch_bounds__(kGrp) void k_back_trial(BaBatch bat) {
     reproject_pre<false>(p.camrec[1 - cur] + kCamRec * p.obs_cam[o], snp[p.obs_pt[o] - p0],
                          p.obs_q + 2 * o, r, J);
     clamp_rows<false>(r, J);
-    v = r[0] * r[0] + r[1] * r[1];
+    if (ROBUST && p.loss != 0) v = robust_weight<0>(r, nullptr, nullptr, p.loss, p.loss_scale);  // delta^2 rho(z)
+    else v = r[0] * r[0] + r[1] * r[1];
   }
   v = block_sum(v, red);
   pred = block_sum(pred, red);
@@ -4090,6 +4181,10 @@ inline int nblk(int n, int bs) { return (n + bs - 1) / bs; }
 int check_problem(const slam_ba_problem* p) {
   SLAM_REQUIRE(p != nullptr, "slam_ba: null problem");
   SLAM_REQUIRE(p->n_cams > 0 && p->n_pts >= 0 && p->n_obs >= 0, "slam_ba: bad sizes");
+  SLAM_REQUIRE(p->loss >= 0 && p->loss <= 3,
+               "slam_ba: loss %d (0 linear, 1 huber, 2 soft_l1, 3 cauchy)", p->loss);
+  SLAM_REQUIRE(p->loss == 0 || (std::isfinite(p->loss_scale) && p->loss_scale > 0.0),
+               "slam_ba: loss %d needs a finite loss_scale > 0, not %g", p->loss, p->loss_scale);
   SLAM_REQUIRE(p->cams[0] && p->cams[1] && p->camrec[0] && p->camrec[1] &&
                    p->cpart && p->bpart && p->grp_ptr && p->grp_cslot && p->grp_bslot &&
                    p->cslot_obs_ptr && p->bslot_pair_ptr && p->cam_cslot_ptr && p->cslot_row && p->bslot_row &&
@@ -4181,6 +4276,7 @@ struct Launch {
   int n, max_grps, max_blocks, max_sgrps, mode;
   size_t solve_lds;
   bool dense;
+  bool robust;  // a problem of the batch has loss != 0: the ROBUST kernels (each branches per problem)
 };
 
 // LDS floor of the one-workgroup camera solve (slam_ba_set_solve_lds_floor): a
@@ -4196,6 +4292,7 @@ static int make_launch(const slam_ba_problem* probs, int n, Launch* L) {
   L->mode = probs[0].lin_mode;
   L->solve_lds = 0;
   L->dense = true;
+  L->robust = false;
   for (int i = 0; i < n; ++i) {
     if (int rc = check_problem(probs + i)) return rc;
     for (int j = 0; j < i; ++j)
@@ -4210,6 +4307,7 @@ static int make_launch(const slam_ba_problem* probs, int n, Launch* L) {
     L->solve_lds = std::max(L->solve_lds, sizeof(double) * BlkLds(9 * probs[i].n_cams).total);
     L->solve_lds = std::max(L->solve_lds, g_solve_lds_floor);
     L->dense = L->dense && !sys_packed(probs[i].n_cams);
+    L->robust = L->robust || probs[i].loss != 0;
   }
   SLAM_REQUIRE(n == 1 || L->dense,
                "slam_ba: batched problems must use the one-workgroup solver (9C <= %d)", kLdsMaxN);
@@ -4227,10 +4325,12 @@ static int launch_build(const Launch& L, hipStream_t s) {
   bool folded = L.mode == 1;
   for (int i = 0; i < L.n; ++i) folded = folded && L.b.p[i].asm_tab != nullptr;
   if (L.mode == 1) {
-    k_lin_mfma<<<dim3(L.max_sgrps, L.n), kMWG, 0, s>>>(L.b);
+    if (L.robust) k_lin_mfma<true><<<dim3(L.max_sgrps, L.n), kMWG, 0, s>>>(L.b);
+    else k_lin_mfma<false><<<dim3(L.max_sgrps, L.n), kMWG, 0, s>>>(L.b);
     SLAM_LAUNCHED("k_lin_mfma");
   } else {
-    k_linearize<<<dim3(L.max_grps, L.n), kLinWG, 0, s>>>(L.b);
+    if (L.robust) k_linearize<true><<<dim3(L.max_grps, L.n), kLinWG, 0, s>>>(L.b);
+    else k_linearize<false><<<dim3(L.max_grps, L.n), kLinWG, 0, s>>>(L.b);
     SLAM_LAUNCHED("k_linearize");
   }
   if (!folded) {  // k_lin_mfma skips the fold of a problem without asm_tab
@@ -4251,10 +4351,14 @@ static int launch_solve(const Launch& L, bool fuse_decide, hipStream_t s) {
       if (int rc = tl_solve_levels(L.b.p[0], s)) return rc;
     }
   }
-  if (fuse_decide)
-    k_back_trial<true><<<dim3(L.max_grps, L.n), kGrp, 0, s>>>(L.b);
-  else
-    k_back_trial<false><<<dim3(L.max_grps, L.n), kGrp, 0, s>>>(L.b);
+  if (L.robust) {
+    if (fuse_decide) k_back_trial<true, true><<<dim3(L.max_grps, L.n), kGrp, 0, s>>>(L.b);
+    else k_back_trial<false, true><<<dim3(L.max_grps, L.n), kGrp, 0, s>>>(L.b);
+  } else if (fuse_decide) {
+    k_back_trial<true, false><<<dim3(L.max_grps, L.n), kGrp, 0, s>>>(L.b);
+  } else {
+    k_back_trial<false, false><<<dim3(L.max_grps, L.n), kGrp, 0, s>>>(L.b);
+  }
   SLAM_LAUNCHED("k_back_trial");
   return SLAM_OK;
 }

@@ -138,7 +138,8 @@ extern "C" int slam_ba_stage_windows(int n_win, int n, int cap, const double* ro
     const int32_t* tab = I + w32;
     const int32_t* stand = I + w32 + nb;
     slam_ba_problem& s = probs[w];
-    std::memset(&s, 0, sizeof(s));
+    std::memset(&s, 0, sizeof(s));  // every field, padding included: loss 0 (linear), no mask
+    s.loss = 0;  // BAWindowSet.stage writes the call's loss and loss_scale afterwards
     s.n_cams = C;
     s.n_pts = P;
     s.n_obs = O;

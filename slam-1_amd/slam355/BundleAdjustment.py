@@ -135,16 +135,19 @@ def bundle_adjustment_sparsity(*args):
     return _bal_sparsity(*args)
 
 
-def bundle_adjustment_with_sparsity(*args, fixed=None):
+def bundle_adjustment_with_sparsity(*args, fixed=None, loss=None, f_scale=1.0):
     """bundle_adjustment_with_sparsity(car_params, sparse_mat) (:179, pose chain,
     ftol 0.1 as the reference) or (cam_params, Qs, cam_idxs, Q_idxs, qs,
     sparse_mat) (:397, BAL).  Both return (residual_init, res.fun, res.x).
-    fixed (BAL form only): camera parameters held constant, slam355.ba.fixed_mask."""
+    fixed (BAL form only): camera parameters held constant, slam355.ba.fixed_mask.
+    loss, f_scale (BAL form only): robust loss per observation, slam355.ba.loss_args."""
     if len(args) == 2:
         if fixed is not None:
             raise ValueError("fixed applies to the BAL form only")
+        if loss is not None or f_scale != 1.0:
+            raise ValueError("loss and f_scale apply to the BAL form only")
         return _chain_solve(args[0], args[1], loop=True)
-    return _bal_with_sparsity(*args, fixed=fixed)
+    return _bal_with_sparsity(*args, fixed=fixed, loss=loss, f_scale=f_scale)
 
 
 # ----------------------------------------------------------------------------- BAL block
@@ -176,10 +179,11 @@ def _bal_sparsity(n_cams, n_Qs, cam_idxs, Q_idxs):
     return (A > 0).astype(int).tolil()
 
 
-def _solve(cam_params, Qs, cam_idxs, Q_idxs, qs, max_iters=200, ftol=1e-12, fixed=None):
+def _solve(cam_params, Qs, cam_idxs, Q_idxs, qs, max_iters=200, ftol=1e-12, fixed=None,
+           loss=None, f_scale=1.0):
     cam_params = np.asarray(cam_params, np.float64).reshape(-1, 9)
     Qs = np.asarray(Qs, np.float64).reshape(-1, 3)
-    prob = _ba.BAProblem(cam_params, Qs, cam_idxs, Q_idxs, qs, fixed=fixed)
+    prob = _ba.BAProblem(cam_params, Qs, cam_idxs, Q_idxs, qs, fixed=fixed, loss=loss, f_scale=f_scale)
     params0 = np.hstack((cam_params.ravel(), Qs.ravel()))
     residual_init = _bal_objective(params0, len(cam_params), len(Qs), cam_idxs, Q_idxs, qs)
     prob.solve(max_iters=max_iters, ftol=ftol)
@@ -189,16 +193,20 @@ def _solve(cam_params, Qs, cam_idxs, Q_idxs, qs, max_iters=200, ftol=1e-12, fixe
     return residual_init, fun, x
 
 
-def bundle_adjustment(cam_params, Qs, cam_idxs, Q_idxs, qs, fixed=None):
+def bundle_adjustment(cam_params, Qs, cam_idxs, Q_idxs, qs, fixed=None, loss=None, f_scale=1.0):
     """(:372-377) -> (residual_init, res.fun, res.x).  fixed: camera parameters
-    held constant (slam355.ba.fixed_mask: None, a [9] pattern, or [C, 9])."""
-    return _solve(cam_params, Qs, cam_idxs, Q_idxs, qs, fixed=fixed)
+    held constant (slam355.ba.fixed_mask: None, a [9] pattern, or [C, 9]).
+    loss, f_scale: robust loss per observation (slam355.ba.loss_args; the
+    names and rho of scipy's least_squares, which the reference calls with its
+    default "linear").  The returned residuals are raw, like scipy's res.fun."""
+    return _solve(cam_params, Qs, cam_idxs, Q_idxs, qs, fixed=fixed, loss=loss, f_scale=f_scale)
 
 
-def _bal_with_sparsity(cam_params, Qs, cam_idxs, Q_idxs, qs, sparse_mat, fixed=None):
+def _bal_with_sparsity(cam_params, Qs, cam_idxs, Q_idxs, qs, sparse_mat, fixed=None, loss=None,
+                       f_scale=1.0):
     """(:397-402) -> (residual_init, res.fun, res.x).  `sparse_mat` is checked
     for shape only: the GPU solver builds the same 2x12 block structure."""
     n = np.asarray(cam_params).size + np.asarray(Qs).size
     if sparse_mat is not None and tuple(sparse_mat.shape) != (2 * len(np.ravel(cam_idxs)), n):
         raise ValueError("sparse_mat shape does not match the problem")
-    return _solve(cam_params, Qs, cam_idxs, Q_idxs, qs, fixed=fixed)
+    return _solve(cam_params, Qs, cam_idxs, Q_idxs, qs, fixed=fixed, loss=loss, f_scale=f_scale)

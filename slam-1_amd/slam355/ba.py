@@ -13,6 +13,11 @@ Held parameters: `fixed` (BAProblem, BAWindowSet.build / stage) names camera
 parameters that stay constant -- the gauge (the oldest keyframes held whole) or
 a calibrated camera's f, k1, k2 (FIXED_INTRINSICS); see fixed_mask.  Every rank
 of a sharded problem must pass the same mask.
+
+Robust loss: `loss`, `f_scale` (BAProblem, BAWindowSet.build / stage) weigh
+every observation by a robust kernel of its 2-vector reprojection error
+(LOSSES, loss_args: scipy's names and rho).  Every rank of a
+sharded problem must pass the same loss.
 """
 from __future__ import annotations
 
@@ -73,6 +78,31 @@ def fixed_mask(n_cams, fixed):
         raise ValueError(f"fixed must have shape (9,) or ({n_cams}, 9), not {f.shape}")
     bits = (f != 0).astype(np.uint32) << np.arange(9, dtype=np.uint32)
     return np.ascontiguousarray(bits.sum(1, dtype=np.uint32))
+
+
+# ----------------------------------------------------------------------------- robust loss
+LOSSES = {"linear": 0, "huber": 1, "soft_l1": 2, "cauchy": 3}  # slam_ba_problem.loss
+
+
+def loss_args(loss, f_scale=1.0):
+    """(code, scale) of slam_ba_problem.loss / loss_scale.  loss: None or a
+    name of LOSSES (scipy least_squares' names and rho(z), z = |r|^2 /
+    f_scale^2 of an observation's clamped 2-vector residual; the cost is
+    0.5 f_scale^2 sum rho(z), the step the Gauss-Newton / IRLS one on
+    sqrt(rho') r, sqrt(rho') J).  f_scale: the residual norm in pixels where
+    the loss turns over, finite and > 0.  None and "linear" give code 0, the
+    plain 0.5 |r|^2 and the code path of a problem built without the keyword."""
+    if loss is None:
+        loss = "linear"
+    if not isinstance(loss, str) or loss not in LOSSES:
+        raise ValueError(f"loss must be one of {sorted(LOSSES)} or None, not {loss!r}")
+    try:
+        scale = float(f_scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"f_scale must be a number, not {f_scale!r}") from None
+    if not (np.isfinite(scale) and scale > 0.0):
+        raise ValueError(f"f_scale must be finite and > 0, not {f_scale!r}")
+    return LOSSES[loss], scale
 
 
 # ----------------------------------------------------------------------------- planner
@@ -1024,8 +1054,13 @@ class BAProblem:
 
     def __init__(self, cams, pts, cam_idx, pt_idx, qs, *, lam0=1e-4, stream=None,
                  block_list=None, lin_mode="auto", chunks_per_wg=None, tl_mode="flow",
-                 fold_assembly=False, tile_mode=None, active_blocks=True, fixed=None):
-        """fixed: camera parameters held constant (fixed_mask: None, a [9]
+                 fold_assembly=False, tile_mode=None, active_blocks=True, fixed=None,
+                 loss=None, f_scale=1.0):
+        """loss, f_scale: robust loss per observation (loss_args: None /
+        "linear", "huber", "soft_l1", "cauchy"; f_scale in pixels); `prob.loss`
+        is the name, `prob.f_scale` the scale.  COST / COST_NEW of state() are
+        then 0.5 f_scale^2 sum rho(z); residuals() stays raw.
+        fixed: camera parameters held constant (fixed_mask: None, a [9]
         pattern such as FIXED_INTRINSICS, or [C, 9]); `prob.fixed` is the
         uint32 [C] mask (None when nothing is held).  With None every result
         is the one a problem without the keyword gives.
@@ -1054,6 +1089,8 @@ class BAProblem:
         C, P = len(cams), len(pts)
         cam_idx, pt_idx, qs = _check_indices(C, P, cam_idx, pt_idx, qs)
         self.fixed = None if fixed is None else fixed_mask(C, fixed)
+        code, self.f_scale = loss_args(loss, f_scale)
+        self.loss = "linear" if loss is None else loss
         pl = None
         if lin_mode in ("auto", "mfma"):
             pl = plan_mfma_native(C, P, cam_idx, pt_idx, block_list, chunks_per_wg)
@@ -1147,6 +1184,7 @@ class BAProblem:
             s.tl_sched_host = self._sched_host.ctypes.data
         if self.fixed is not None:
             s.cam_fixed = t["cam_fixed"].data_ptr()
+        s.loss, s.loss_scale = code, self.f_scale
         if pl["mode"] == 1 and fold_assembly:  # k_lin_mfma assembles sys itself
             t["asm_tab"] = T(assembly_table(C, pl))
             s.asm_tab = t["asm_tab"].data_ptr()
@@ -1558,7 +1596,8 @@ class BAWindowSet:
         offs = {k: int(m[base + i]) for i, k in enumerate(_lib.PLAN_TABLES)}
         return d64, d32, o64, int(m[9]), int(m[10]), offs
 
-    def stage(self, rows, cnt, maps, M, cams, u_off, v_off, stream, lam0=1e-4, fixed=None):
+    def stage(self, rows, cnt, maps, M, cams, u_off, v_off, stream, lam0=1e-4, fixed=None,
+              loss=None, f_scale=1.0):
         """The tracked windows of one batch, staged by ONE native call
         (slam_ba_stage_windows: every window's observations from the mapper's
         rows, its plan, its float64 data and tables into the pinned staging
@@ -1570,7 +1609,10 @@ class BAWindowSet:
         problems in window order (BAProblem interface).  fixed: held camera
         parameters, one [9] or [n, 9] pattern for every window of the call
         (fixed_mask); its device words are written into the descriptors after
-        the native call, whose staged layout does not change."""
+        the native call, whose staged layout does not change.  loss, f_scale:
+        the robust loss of every window of the call (loss_args), written into
+        the descriptors in the same place."""
+        code, scale = loss_args(loss, f_scale)
         rows = np.ascontiguousarray(rows, np.float64)
         cnt = np.ascontiguousarray(cnt, np.int32)
         maps = np.ascontiguousarray(maps, np.float64)
@@ -1634,7 +1676,7 @@ class BAWindowSet:
                 qs = np.stack([om[:, 2] - u_off, om[:, 3] - v_off], 1)
                 out.append(BAProblem(cams[w * n:w * n + n].copy(), maps[w, :int(M[w])].copy(),
                                      om[:, 0].astype(np.int64), om[:, 1].astype(np.int64), qs,
-                                     lam0=lam0, stream=stream, fixed=fixed))
+                                     lam0=lam0, stream=stream, fixed=fixed, loss=loss, f_scale=f_scale))
                 continue
             bp = self._window(slot)
             bp._t, bp._perm, bp._views = None, None, None
@@ -1646,17 +1688,21 @@ class BAWindowSet:
             bp.fixed, bp._fixed_t = fwords, fdev
             if fdev is not None:
                 bp._s_raw.cam_fixed = fdev.data_ptr()
+            bp.loss, bp.f_scale = "linear" if loss is None else loss, scale
+            bp._s_raw.loss, bp._s_raw.loss_scale = code, scale
             out.append(bp)
         built = [p for p in out if isinstance(p, _WindowProblem)]
         for i in range(0, len(built), BABatch.MAX_BATCH):
             BABatch(built[i:i + BABatch.MAX_BATCH], stream=stream).reset(lam0)
         return out
 
-    def build(self, problems, stream, lam0=1e-4, fixed=None):
+    def build(self, problems, stream, lam0=1e-4, fixed=None, loss=None, f_scale=1.0):
         """The windows `problems` [(cams, pts, cam_idx, pt_idx, qs), ...] built
         together (see the class); fixed: held camera parameters, one [9] or
-        [n, 9] pattern shared by every window of the call (fixed_mask)."""
+        [n, 9] pattern shared by every window of the call (fixed_mask); loss,
+        f_scale: the robust loss of every window of the call (loss_args)."""
         problems = list(problems)
+        code, scale = loss_args(loss, f_scale)
         fwords, fdev = self._fixed_dev([len(np.reshape(pr[0], (-1, 9))) for pr in problems],
                                        fixed, stream)
         specs, extra = [], []
@@ -1668,7 +1714,8 @@ class BAWindowSet:
             ci, pi, qs = _check_indices(C, P, ci, pi, qs)
             pl = plan_mfma_native(C, P, ci, pi) if 9 * C <= LDS_MAX_N else None
             if pl is None:
-                extra.append(BAProblem(cams, pts, ci, pi, qs, lam0=lam0, stream=stream, fixed=fixed))
+                extra.append(BAProblem(cams, pts, ci, pi, qs, lam0=lam0, stream=stream, fixed=fixed,
+                                       loss=loss, f_scale=f_scale))
                 continue
             if pl["perm"] is not None:
                 pts = pts[pl["perm"]]
@@ -1750,6 +1797,8 @@ class BAWindowSet:
             bp._fixed_t = fdev
             if fdev is not None:
                 s.cam_fixed = fdev.data_ptr()
+            bp.loss, bp.f_scale = "linear" if loss is None else loss, scale
+            s.loss, s.loss_scale = code, scale
             bp._s_raw = s
             out[w] = bp
         it = iter(extra)
