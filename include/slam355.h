@@ -561,6 +561,33 @@ int slam_ba_reset(const slam_ba_problem* prob, double lambda0, void* stream);
  * one-workgroup solver (9C <= 120); a packed problem iterates on its own. */
 int slam_ba_iterate_batch(const slam_ba_problem* probs, int n_probs, int n_iter, void* stream);
 
+/* Marginal covariance of the camera parameters: 9x9 blocks of
+ * S0^-1, where S0 = U - W V^-1 W^T is the reduced camera system at the live
+ * parameters with ZERO damping, built from the same clamped, masked, robust-
+ * weighted Jacobian as every LM step -- the camera part of (J^T J)^-1, in the
+ * units of unit-variance pixel noise.  d_pairs [n_pairs][2] camera indices
+ * (a, b), in range (checked by the host wrapper); d_cov [n_pairs][9][9]
+ * row-major, block q = Cov(camera a, camera b) (a == b: a marginal block,
+ * exactly symmetric; block (a, b) is block (b, a) transposed bit for bit).
+ * Rows and columns of held parameters (cam_fixed) are +0.0.  The caller fixes
+ * the gauge (two cameras held whole suffice for the BAL model): d_status[0] = 1
+ * and every output NaN when S0 is not numerically positive definite, i.e. a
+ * pivot of the unpivoted Cholesky is not finite or L_kk^2 <= rank_tol * S0_kk
+ * (rank_tol finite, in [0, 1)); 0 otherwise.  A point whose 3x3 block is
+ * singular at lambda = 0 contributes with a zero inverse (as in the LM steps).
+ * d_ws: slam_ba_cov_workspace_len(n_cams) doubles (two dense matrices of
+ * ceil(9C / 64) 64x64 tile rows), ws_len its length.  Asynchronous on
+ * `stream`, no allocation, no host sync; lambda and every other LM state slot
+ * are as before afterwards, but prob->sys is overwritten: a
+ * slam_ba_build_system made before must be repeated before
+ * slam_ba_solve_step (slam_ba_iterate rebuilds anyway).  Single rank: the
+ * system of a landmark shard is not summed over ranks here.  Landmark
+ * covariances are not computed. */
+long long slam_ba_cov_workspace_len(int n_cams);
+int slam_ba_covariance(const slam_ba_problem* prob, const int32_t* d_pairs, int n_pairs,
+                       double rank_tol, double* d_cov, double* d_ws, long long ws_len,
+                       int32_t* d_status, void* stream);
+
 /* Minimum dynamic LDS (bytes, <= 160 KiB) the one-workgroup camera solve
  * (9C <= 120) requests; 0 (default) = what it needs.  A floor above what
  * co-resident workgroups of other streams leave (e.g. > 80 KiB beside an ORB

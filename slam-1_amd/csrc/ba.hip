@@ -4439,6 +4439,370 @@ extern "C" int slam_ba_iterate_batch(const slam_ba_problem* probs, int n_probs, 
   return SLAM_OK;
 }
 
+// ---------------------------------------------------------------- camera covariance
+// Marginal covariance of the camera parameters: 9x9 blocks of S0^-1, S0 the
+// reduced camera system at lambda = 0.  The build runs unchanged
+// between two one-lane kernels that park lambda; S0 is gathered into lower
+// 64x64 tiles of a dense matrix in natural camera order (held and padding rows:
+// unit diagonal, no coupling), factored by a blocked right-looking Cholesky over
+// tile columns (k_cov_panel / k_cov_update, the tile factor of the tiled
+// solve), L^-1 formed by tile rows (k_cov_minv), and the requested tiles of
+// L^-T L^-1 (k_cov_sigma) picked into the output blocks (k_cov_pick).  Not a
+// per-iteration path: one workgroup per tile, O(T) launches, nothing resident.
+namespace {
+
+struct CovLayout {  // doubles inside the workspace; T = ceil(9C / 64)
+  int T, N;
+  long long a, m, diag, need, hdr, total;
+  __host__ __device__ explicit CovLayout(int n_cams) {
+    T = (9 * n_cams + kTB - 1) / kTB;
+    N = T * kTB;
+    a = 0;                              // S0 -> L (lower tiles), then the tiles of Sigma
+    m = a + (long long)N * N;           // L^-1 (lower tiles; the diagonal tiles hold L_kk^-1)
+    diag = m + (long long)N * N;        // diagonal of S0 (1 on held and padding rows)
+    need = diag + N;                    // ints [T][T]: lower tile (I, J) holds a requested entry
+    hdr = need + ((long long)T * T + 1) / 2;  // [0] the parked lambda, [1] (int) status
+    total = hdr + 8;
+  }
+};
+
+__device__ __forceinline__ bool cov_free(const slam_ba_problem& p, int r) {
+  if (r >= 9 * p.n_cams) return false;
+  return p.cam_fixed == nullptr || ((p.cam_fixed[r / 9] >> (r % 9)) & 1u) == 0;
+}
+__device__ __forceinline__ bool cov_failed(const double* ws, const CovLayout& L) {
+  return *reinterpret_cast<const volatile int*>(ws + L.hdr + 1) != 0;
+}
+// lower tile (I, J), I >= J, of linear index idx = I (I + 1) / 2 + J
+__device__ __forceinline__ int2 cov_tile_of(int idx) {
+  int I = (int)((sqrtf(8.0f * (float)idx + 1.0f) - 1.0f) * 0.5f);
+  while ((I + 1) * (I + 2) / 2 <= idx) ++I;
+  while (I * (I + 1) / 2 > idx) --I;
+  return int2{I, idx - I * (I + 1) / 2};
+}
+
+// fragment-ordered LDS image of the TRANSPOSE of a 64x64 tile (frag_idx(c, r)
+// holds g[r][c]): as the second MFMA operand it gives X Y, as the first Y^T X
+__device__ __forceinline__ void tile_to_frag_t(const double* __restrict__ g, int ld, double* f) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r = lane & 15, c = lane >> 4;
+  for (int f0 = w; f0 < 64; f0 += 16 * (kTlWG / 64)) {
+    double tmp[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      const int fi = f0 + q * (kTlWG / 64);
+      tmp[q] = g[(size_t)(4 * (fi & 15) + c) * ld + 16 * (fi >> 4) + r];
+    }
+#pragma unroll
+    for (int q = 0; q < 16; ++q) f[((f0 + q * (kTlWG / 64)) << 6) + lane] = tmp[q];
+  }
+}
+
+// acc[s] (wave w) += rows 16w.., cols 16s.. of the product of two fragment images
+__device__ __forceinline__ void cov_gemm(const double* Xf, const double* Yf, d4 acc[4], bool neg = false) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll 4
+  for (int kk = 0; kk < 16; ++kk) {
+    const double a0 = Xf[((w * 16 + kk) << 6) + lane];
+    const double a = neg ? -a0 : a0;
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+      acc[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Yf[((s * 16 + kk) << 6) + lane], acc[s], 0, 0, 0);
+  }
+}
+__device__ __forceinline__ void cov_store(double* C, int ld, const d4 acc[4], bool sub = false) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      double* c = C + (size_t)(w * 16 + (lane >> 4) + 4 * r) * ld + s * 16 + (lane & 15);
+      *c = sub ? *c - acc[s][r] : acc[s][r];
+    }
+}
+
+// restore == 0: lambda parked in the workspace and set to 0, status cleared;
+// restore == 1: lambda back.  No other state slot is touched.
+__global__ void k_cov_lambda(slam_ba_problem p, double* ws, int restore) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const CovLayout L(p.n_cams);
+  if (restore) {
+    p.state[SLAM_BA_ST_LAMBDA] = ws[L.hdr];
+  } else {
+    ws[L.hdr] = p.state[SLAM_BA_ST_LAMBDA];
+    p.state[SLAM_BA_ST_LAMBDA] = 0.0;
+    *reinterpret_cast<int*>(ws + L.hdr + 1) = 0;
+  }
+}
+
+// One workgroup per lower tile: S0 from the dense sys (zeros for a packed one,
+// k_cov_scatter follows), identity on held and padding rows; the diagonal of S0.
+__global__ __launch_bounds__(kTlWG) void k_cov_load(slam_ba_problem p, double* ws) {
+  const CovLayout L(p.n_cams);
+  const int n = 9 * p.n_cams;
+  const int2 IJ = cov_tile_of(blockIdx.x);
+  const bool dense = !sys_packed(p.n_cams);
+  double* A = ws + L.a;
+  for (int e = threadIdx.x; e < kTB * kTB; e += kTlWG) {
+    const int i = IJ.x * kTB + (e >> 6), j = IJ.y * kTB + (e & 63);
+    double v = i == j ? 1.0 : 0.0;
+    if (cov_free(p, i) && cov_free(p, j)) v = dense ? p.sys[(size_t)i * n + j] : 0.0;
+    A[(size_t)i * L.N + j] = v;
+  }
+  if (IJ.x == IJ.y && threadIdx.x < kTB) {
+    const int i = IJ.x * kTB + threadIdx.x;
+    if (!cov_free(p, i)) ws[L.diag + i] = 1.0;
+    else if (dense) ws[L.diag + i] = p.sys[(size_t)i * n + i];
+  }
+  if (threadIdx.x == 0) reinterpret_cast<int*>(ws + L.need)[IJ.x * L.T + IJ.y] = 0;
+}
+
+// One workgroup per packed block: its free entries into the lower tiles (both
+// triangles inside a diagonal tile), the diagonal of S0.
+__global__ __launch_bounds__(128) void k_cov_scatter(slam_ba_problem p, double* ws) {
+  const CovLayout L(p.n_cams);
+  const int blk = blockIdx.x, t = threadIdx.x;
+  if (t >= 81) return;
+  const int c1 = p.blocks[2 * blk], c2 = p.blocks[2 * blk + 1];
+  const int r = 9 * c1 + t / 9, c = 9 * c2 + t % 9;
+  if (!cov_free(p, r) || !cov_free(p, c)) return;
+  const double v = p.sys[(size_t)blk * 81 + t];
+  double* A = ws + L.a;
+  const int tr = r / kTB, tc = c / kTB;
+  if (tr >= tc) A[(size_t)r * L.N + c] = v;
+  if (c1 != c2 && tc >= tr) A[(size_t)c * L.N + r] = v;
+  if (r == c) ws[L.diag + r] = v;
+}
+
+// The lower tiles that hold an entry of a requested block (a block may straddle tiles).
+__global__ __launch_bounds__(kBS) void k_cov_mark(slam_ba_problem p, const int32_t* __restrict__ pairs,
+                                                  int n_pairs, double* ws) {
+  const CovLayout L(p.n_cams);
+  const int q = blockIdx.x * kBS + threadIdx.x;
+  if (q >= n_pairs) return;
+  const int a = pairs[2 * q], b = pairs[2 * q + 1];
+  if ((unsigned)a >= (unsigned)p.n_cams || (unsigned)b >= (unsigned)p.n_cams) return;
+  int* need = reinterpret_cast<int*>(ws + L.need);
+  for (int ta = 9 * a / kTB; ta <= (9 * a + 8) / kTB; ++ta)
+    for (int tb = 9 * b / kTB; tb <= (9 * b + 8) / kTB; ++tb) need[max(ta, tb) * L.T + min(ta, tb)] = 1;
+}
+
+// Tile column k, one workgroup per tile (I, k), I = k + blockIdx.x: every one
+// factors A_kk (tile_chol_inv_blk: L_kk^-1); the diagonal one stores L_kk^-1 as
+// the diagonal tile of L^-1 and runs the relative-pivot test, the others form
+// L_Ik = A_Ik L_kk^-T in place.
+__global__ __launch_bounds__(kTlWG) __attribute__((amdgpu_waves_per_eu(1, 1)))
+void k_cov_panel(slam_ba_problem p, double* ws, int k, double rank_tol) {
+  const CovLayout L(p.n_cams);
+  const int I = k + blockIdx.x;
+  __shared__ double VX[2 * kTB * kTB];
+  double* Vf = VX;                        // L_kk^-1, fragment order
+  __shared__ double Xf[kTB * kTB];        // A_Ik, fragment order
+  __shared__ int okf;
+  // this launch's diagonal workgroup may raise the status while others start:
+  // one lane reads it for the whole workgroup
+  if (threadIdx.x == 0) okf = cov_failed(ws, L) ? 1 : 0;
+  __syncthreads();
+  if (okf != 0) return;
+  __syncthreads();  // okf is written again by the tile factor
+  double* A = ws + L.a;
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const double* Akk = A + (size_t)k * kTB * L.N + k * kTB;
+  double* AIk = A + (size_t)I * kTB * L.N + k * kTB;
+  if (I > k && w >= 2) tile_to_frag(AIk, L.N, Xf, w - 2, 2);
+  double x[kTB];
+  double* Mb = VX;
+  double* Xb = VX + kTB * kMS;
+  double* Tb = Xb + 10 * 16 * kBS17;
+  const int rows = min(kTB, 9 * p.n_cams - k * kTB);
+  const bool ok = tile_chol_inv_blk(Akk, L.N, Mb, Xb, Tb, &okf, (rows + 15) >> 4);
+  if (w == 1) {
+    const int cb16 = lane >> 4;
+#pragma unroll
+    for (int m = 0; m < kTB; ++m)
+      x[m] = (m >> 4) >= cb16 ? Xb[blk_id(m >> 4, cb16) * 16 * kBS17 + (m & 15) * kBS17 + (lane & 15)]
+                              : 0.0;
+  }
+  __syncthreads();  // VX is reused below
+  if (w == 1) {
+    if (I == k) {
+      double* Mkk = ws + L.m + (size_t)k * kTB * L.N + k * kTB;
+#pragma unroll
+      for (int m = 0; m < kTB; ++m) Mkk[(size_t)m * L.N + lane] = x[m];
+      // pivot d = L_cc^2 = 1 / (L_kk^-1)_cc^2 against rank_tol * S0_cc
+      double xd = 0.0;
+#pragma unroll
+      for (int m = 0; m < kTB; ++m) xd = m == lane ? x[m] : xd;
+      const double piv = 1.0 / (xd * xd);
+      const bool bad = !ok || !(xd > 0.0 && xd < INFINITY) || !(piv < INFINITY) ||
+                       piv <= rank_tol * ws[L.diag + k * kTB + lane];
+      if (__any(bad) && lane == 0) *reinterpret_cast<int*>(ws + L.hdr + 1) = 1;
+    } else {
+#pragma unroll
+      for (int m = 0; m < kTB; ++m) Vf[frag_idx(m, lane)] = x[m];
+    }
+  }
+  if (I == k || !ok) return;
+  __syncthreads();
+  d4 acc[4];
+  gemm_xyT_lowY(Xf, Vf, acc);  // L_Ik = A_Ik (L_kk^-1)^T
+  cov_store(AIk, L.N, acc);
+}
+
+// Trailing update of column k, one workgroup per tile (I, J), I >= J > k:
+// A_IJ -= L_Ik L_Jk^T.
+__global__ __launch_bounds__(kTlWG) void k_cov_update(slam_ba_problem p, double* ws, int k) {
+  const CovLayout L(p.n_cams);
+  if (cov_failed(ws, L)) return;
+  const int2 IJ = cov_tile_of(blockIdx.x);
+  const int I = k + 1 + IJ.x, J = k + 1 + IJ.y;
+  __shared__ double Xf[kTB * kTB], Yf[kTB * kTB];
+  double* A = ws + L.a;
+  tile_to_frag(A + (size_t)I * kTB * L.N + k * kTB, L.N, Xf);
+  if (I != J) tile_to_frag(A + (size_t)J * kTB * L.N + k * kTB, L.N, Yf);
+  __syncthreads();
+  d4 acc[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) acc[s] = d4{0.0, 0.0, 0.0, 0.0};
+  cov_gemm(Xf, I == J ? Xf : Yf, acc);
+  cov_store(A + (size_t)I * kTB * L.N + J * kTB, L.N, acc, true);
+}
+
+// Tile row i of M = L^-1, one workgroup per tile (i, j), j < i:
+// M_ij = -L_ii^-1 sum_{k=j}^{i-1} L_ik M_kj  (rows < i of M are complete).
+__global__ __launch_bounds__(kTlWG) void k_cov_minv(slam_ba_problem p, double* ws, int i) {
+  const CovLayout L(p.n_cams);
+  if (cov_failed(ws, L)) return;
+  const int j = blockIdx.x;
+  __shared__ double Xf[kTB * kTB], Yf[kTB * kTB];
+  const double* A = ws + L.a;
+  double* M = ws + L.m;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  d4 acc[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) acc[s] = d4{0.0, 0.0, 0.0, 0.0};
+  for (int k = j; k < i; ++k) {
+    tile_to_frag(A + (size_t)i * kTB * L.N + k * kTB, L.N, Xf);
+    tile_to_frag_t(M + (size_t)k * kTB * L.N + j * kTB, L.N, Yf);
+    __syncthreads();
+    cov_gemm(Xf, Yf, acc);
+    __syncthreads();  // Xf / Yf reloaded next k
+  }
+  tile_to_frag(M + (size_t)i * kTB * L.N + i * kTB, L.N, Xf);
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      Yf[frag_idx(s * 16 + (lane & 15), w * 16 + (lane >> 4) + 4 * r)] = acc[s][r];  // the sum, transposed image
+  __syncthreads();
+#pragma unroll
+  for (int s = 0; s < 4; ++s) acc[s] = d4{0.0, 0.0, 0.0, 0.0};
+  cov_gemm(Xf, Yf, acc, true);
+  cov_store(M + (size_t)i * kTB * L.N + j * kTB, L.N, acc);
+}
+
+// Sigma_IJ = sum_{k >= I} M_kI^T M_kJ for the marked lower tiles (I >= J), into
+// the tiles of the factor (dead by now).
+__global__ __launch_bounds__(kTlWG) void k_cov_sigma(slam_ba_problem p, double* ws) {
+  const CovLayout L(p.n_cams);
+  if (cov_failed(ws, L)) return;
+  const int2 IJ = cov_tile_of(blockIdx.x);
+  const int I = IJ.x, J = IJ.y;
+  if (reinterpret_cast<const int*>(ws + L.need)[I * L.T + J] == 0) return;
+  __shared__ double Xf[kTB * kTB], Yf[kTB * kTB];
+  const double* M = ws + L.m;
+  d4 acc[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) acc[s] = d4{0.0, 0.0, 0.0, 0.0};
+  for (int k = I; k < L.T; ++k) {
+    tile_to_frag_t(M + (size_t)k * kTB * L.N + I * kTB, L.N, Xf);
+    if (I != J) tile_to_frag_t(M + (size_t)k * kTB * L.N + J * kTB, L.N, Yf);
+    __syncthreads();
+    cov_gemm(Xf, I == J ? Xf : Yf, acc);
+    __syncthreads();
+  }
+  cov_store(ws + L.a + (size_t)I * kTB * L.N + J * kTB, L.N, acc);
+}
+
+// One workgroup per requested block: entry (i, j) from the lower triangle of
+// Sigma (so a marginal block is exactly symmetric and block (a, b) is block
+// (b, a) transposed bit for bit), +0.0 on held rows and columns, NaN when the
+// system was not positive definite; the status.
+__global__ __launch_bounds__(128) void k_cov_pick(slam_ba_problem p, const int32_t* __restrict__ pairs,
+                                                  const double* __restrict__ ws, double* __restrict__ cov,
+                                                  int32_t* __restrict__ status) {
+  const CovLayout L(p.n_cams);
+  const bool failed = cov_failed(ws, L);
+  const int q = blockIdx.x, t = threadIdx.x;
+  if (q == 0 && t == 0) status[0] = failed ? 1 : 0;
+  if (t >= 81) return;
+  const int a = pairs[2 * q], b = pairs[2 * q + 1];
+  double v = __builtin_nan("");
+  if (!failed && (unsigned)a < (unsigned)p.n_cams && (unsigned)b < (unsigned)p.n_cams) {
+    const int i = 9 * a + t / 9, j = 9 * b + t % 9;
+    v = 0.0;
+    if (cov_free(p, i) && cov_free(p, j)) v = ws[L.a + (size_t)max(i, j) * L.N + min(i, j)];
+  }
+  cov[(size_t)q * 81 + t] = v;
+}
+
+}  // namespace
+
+extern "C" long long slam_ba_cov_workspace_len(int n_cams) {
+  if (n_cams <= 0) return 0;
+  return CovLayout(n_cams).total;
+}
+
+extern "C" int slam_ba_covariance(const slam_ba_problem* prob, const int32_t* d_pairs, int n_pairs,
+                                  double rank_tol, double* d_cov, double* d_ws, long long ws_len,
+                                  int32_t* d_status, void* stream) {
+  Launch La;
+  if (int rc = make_launch(prob, 1, &La)) return rc;
+  SLAM_REQUIRE(n_pairs >= 1, "slam_ba_covariance: n_pairs %d < 1", n_pairs);
+  SLAM_REQUIRE(std::isfinite(rank_tol) && rank_tol >= 0.0 && rank_tol < 1.0,
+               "slam_ba_covariance: rank_tol %g must be finite and in [0, 1)", rank_tol);
+  SLAM_REQUIRE(d_pairs && d_cov && d_status, "slam_ba_covariance: null pointer");
+  const CovLayout L(prob->n_cams);
+  SLAM_REQUIRE(d_ws != nullptr && ws_len >= L.total,
+               "slam_ba_covariance: workspace of %lld doubles, slam_ba_cov_workspace_len gives %lld",
+               d_ws ? ws_len : 0ll, L.total);
+  hipStream_t s = slam::as_stream(stream);
+  const slam_ba_problem& p = La.b.p[0];
+  const int T = L.T;
+  k_cov_lambda<<<1, 64, 0, s>>>(p, d_ws, 0);
+  SLAM_LAUNCHED("k_cov_lambda");
+  const int rc = launch_build(La, s);
+  k_cov_lambda<<<1, 64, 0, s>>>(p, d_ws, 1);  // also after a failed launch: lambda goes back
+  SLAM_LAUNCHED("k_cov_lambda");
+  if (rc) return rc;
+  k_cov_load<<<T * (T + 1) / 2, kTlWG, 0, s>>>(p, d_ws);
+  SLAM_LAUNCHED("k_cov_load");
+  if (sys_packed(p.n_cams)) {
+    k_cov_scatter<<<p.n_blocks, 128, 0, s>>>(p, d_ws);
+    SLAM_LAUNCHED("k_cov_scatter");
+  }
+  k_cov_mark<<<nblk(n_pairs, kBS), kBS, 0, s>>>(p, d_pairs, n_pairs, d_ws);
+  SLAM_LAUNCHED("k_cov_mark");
+  for (int k = 0; k < T; ++k) {
+    k_cov_panel<<<T - k, kTlWG, 0, s>>>(p, d_ws, k, rank_tol);
+    SLAM_LAUNCHED("k_cov_panel");
+    const int m = T - k - 1;
+    if (m > 0) {
+      k_cov_update<<<m * (m + 1) / 2, kTlWG, 0, s>>>(p, d_ws, k);
+      SLAM_LAUNCHED("k_cov_update");
+    }
+  }
+  for (int i = 1; i < T; ++i) {
+    k_cov_minv<<<i, kTlWG, 0, s>>>(p, d_ws, i);
+    SLAM_LAUNCHED("k_cov_minv");
+  }
+  k_cov_sigma<<<T * (T + 1) / 2, kTlWG, 0, s>>>(p, d_ws);
+  SLAM_LAUNCHED("k_cov_sigma");
+  k_cov_pick<<<n_pairs, 128, 0, s>>>(p, d_pairs, d_ws, d_cov, d_status);
+  SLAM_LAUNCHED("k_cov_pick");
+  return SLAM_OK;
+}
+
 #ifdef SLAM_SOLVE_TRACE
 extern "C" int slam_solve_trace(unsigned long long* out) {
   SLAM_HIP(hipDeviceSynchronize());

@@ -110,6 +110,8 @@ SIGNATURES = {
     "slam_ba_iterate": [_PROB, c_int, c_p],
     "slam_ba_reset": [_PROB, c_double, c_p],
     "slam_ba_iterate_batch": [_PROB, c_int, c_int, c_p],
+    "slam_ba_cov_workspace_len": [c_int],
+    "slam_ba_covariance": [_PROB, c_p, c_int, c_double, c_p, c_p, c_longlong, c_p, c_p],
     "slam_ba_set_solve_lds_floor": [c_int],
     "slam_orb_set_lds_floor": [c_int],
     "slam_count_min": [c_p, c_int, c_p, c_p],
@@ -154,7 +156,8 @@ SIGNATURES = {
 }
 _RESTYPE = {"slam_last_error": ctypes.c_char_p, "slam_ba_sys_len": ctypes.c_longlong,
             "slam_ba_plan_bound": ctypes.c_longlong,
-            "slam_ba_chol_len": ctypes.c_longlong, "slam_pnp_workspace_len": ctypes.c_longlong,
+            "slam_ba_chol_len": ctypes.c_longlong, "slam_ba_cov_workspace_len": ctypes.c_longlong,
+            "slam_pnp_workspace_len": ctypes.c_longlong,
             "slam_fundamental_workspace_len": ctypes.c_longlong,
             "slam_pose_chain_workspace_len": ctypes.c_longlong}
 

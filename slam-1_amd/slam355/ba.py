@@ -18,6 +18,11 @@ Robust loss: `loss`, `f_scale` (BAProblem, BAWindowSet.build / stage) weigh
 every observation by a robust kernel of its 2-vector reprojection error
 (LOSSES, loss_args: scipy's names and rho).  Every rank of a
 sharded problem must pass the same loss.
+
+Covariance: `BAProblem.covariance` / `BABatch.covariance` (cov_pairs) return
+marginal 9x9 covariance blocks of the camera parameters at the live
+parameters, from the reduced camera system at zero damping, inverted on the
+device.  The caller fixes the gauge with `fixed`.
 """
 from __future__ import annotations
 
@@ -103,6 +108,49 @@ def loss_args(loss, f_scale=1.0):
     if not (np.isfinite(scale) and scale > 0.0):
         raise ValueError(f"f_scale must be finite and > 0, not {f_scale!r}")
     return LOSSES[loss], scale
+
+
+# ----------------------------------------------------------------------------- covariance
+def cov_pairs(n_cams, cameras=None, pairs=None):
+    """The int32 [m, 2] block list of slam_ba_covariance: (a, a) for every
+    camera a of `cameras` (their marginal blocks), then the (a, b) of `pairs`
+    (cross blocks Cov(a, b); a == b is allowed).  None, None: every camera's
+    own block.  Raises ValueError on an index outside [0, n_cams), a
+    non-integer or wrongly shaped input, or an empty list."""
+    n_cams = int(n_cams)
+    if n_cams < 1:
+        raise ValueError("n_cams must be >= 1")
+
+    def ints(a, what):
+        a = np.asarray(a)
+        if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+            if a.size:
+                raise ValueError(f"{what} must be integer camera indices")
+            a = a.astype(np.int64)
+        a = a.astype(np.int64)
+        if a.size and (a.min() < 0 or a.max() >= n_cams):
+            raise ValueError(f"{what}: camera index out of range [0, {n_cams})")
+        return a
+
+    if cameras is None and pairs is None:
+        cameras = np.arange(n_cams)
+    out = []
+    if cameras is not None:
+        c = ints(cameras, "cameras")
+        if c.ndim != 1:
+            raise ValueError("cameras must be a 1-D list of camera indices")
+        out.append(np.stack([c, c], 1))
+    if pairs is not None:
+        p = ints(pairs, "pairs")
+        if p.ndim != 2 or p.shape[1] != 2:
+            if p.size:
+                raise ValueError("pairs must have shape [m, 2]")
+            p = p.reshape(0, 2)
+        out.append(p)
+    out = np.concatenate(out).astype(np.int32)
+    if len(out) == 0:
+        raise ValueError("no covariance block requested")
+    return np.ascontiguousarray(out)
 
 
 # ----------------------------------------------------------------------------- planner
@@ -1333,6 +1381,75 @@ class BAProblem:
     def cost(self) -> float:
         return self.state()["COST"]
 
+    def covariance(self, cameras=None, pairs=None, scale="unit", rank_tol=1e-8, device=False):
+        """Marginal covariance blocks of the camera parameters at the live
+        parameters: [m, 9, 9] float64 in the order of cov_pairs(C, cameras,
+        pairs) -- Cov(a, a) per camera of `cameras`, then Cov(a, b) per pair
+        (None, None: every camera's own block).  They are blocks of S0^-1, S0
+        the Schur-reduced camera system with zero damping of the clamped,
+        masked, robust-weighted Jacobian of the LM steps; rows
+        and columns of held parameters are exactly 0.
+        scale: "unit" (unit-variance pixel noise), "residual" (times
+        2 COST / (2 O - n_free), n_free = free camera parameters + 3 P), or a
+        positive float.  The gauge must be fixed by the caller (`fixed`: two
+        cameras held whole suffice): np.linalg.LinAlgError when S0 is not
+        numerically positive definite, i.e. a Cholesky pivot L_kk^2 <=
+        rank_tol S0_kk or not finite.  device=True returns the device tensor
+        without that host check (NaN blocks then; cov_status() reads the
+        status of the last call).  A point whose 3x3 block is singular
+        without damping counts with a zero inverse, as in the LM steps.
+        Landmark covariances are not computed, and a landmark shard's system
+        is not summed over ranks here.
+        Overwrites `sys`: a build_system() made before the call must be
+        repeated before solve_step() (iterate* rebuilds anyway); the LM state
+        and the parameters are untouched.  The workspace (two dense tiled
+        matrices) is allocated on first use and kept."""
+        pr = cov_pairs(self.C, cameras, pairs)
+        if isinstance(scale, str):
+            if scale not in ("unit", "residual"):
+                raise ValueError(f"scale must be 'unit', 'residual' or a positive float, not {scale!r}")
+            fac = None
+        else:
+            fac = float(scale)
+            if not (np.isfinite(fac) and fac > 0.0):
+                raise ValueError(f"scale must be 'unit', 'residual' or a positive float, not {scale!r}")
+        rank_tol = float(rank_tol)
+        if not (np.isfinite(rank_tol) and 0.0 <= rank_tol < 1.0):
+            raise ValueError(f"rank_tol must be finite and in [0, 1), not {rank_tol!r}")
+        s = self._s  # (a BAWindowSet problem: raises once its buffers were reused)
+        dev = self.t["state"].device
+        with torch.cuda.stream(self.stream if self.stream is not None else torch.cuda.current_stream()):
+            if getattr(self, "_cov_ws", None) is None:
+                n = int(_lib.lib.slam_ba_cov_workspace_len(self.C))
+                self._cov_ws = torch.empty(n, dtype=torch.float64, device=dev)
+                self._cov_status = torch.zeros(1, dtype=torch.int32, device=dev)
+            tp = torch.from_numpy(pr).to(dev)
+            out = torch.empty((len(pr), 9, 9), dtype=torch.float64, device=dev)
+            _lib.call("slam_ba_covariance", ctypes.byref(s), ptr(tp), len(pr), rank_tol, ptr(out),
+                      ptr(self._cov_ws), self._cov_ws.numel(), ptr(self._cov_status), self._sp())
+            if scale == "residual":
+                n_free = 9 * self.C + 3 * self.P
+                if self.fixed is not None:
+                    n_free -= sum(_popcount(int(w) & 0x1FF) for w in self.fixed)
+                dof = 2 * self.O - n_free
+                if dof <= 0:
+                    raise ValueError(f"scale 'residual': 2 O - n_free = {dof} degrees of freedom")
+                fac = 2.0 * self.state()["COST"] / dof
+            if fac is not None:
+                out *= fac
+            if device:
+                return out
+            host = out.cpu().numpy()
+        if self.cov_status() != 0:
+            raise np.linalg.LinAlgError(
+                "BA covariance: the reduced camera system is not positive definite at "
+                f"rank_tol {rank_tol:g} (fix the gauge: hold two cameras whole)")
+        return host
+
+    def cov_status(self) -> int:
+        """Status of the last covariance() call: 0 ok, 1 not positive definite."""
+        return int(self._cov_status.item())
+
     def solve(self, max_iters=100, ftol=1e-10, check_every=5):
         """Iterate until a batch of `check_every` iterations that accepted at
         least one step lowered the cost by less than ftol (relative), until
@@ -1430,6 +1547,11 @@ class BABatch:
 
     def states(self):
         return [p.state() for p in self.problems]
+
+    def covariance(self, cameras=None, pairs=None, scale="unit", rank_tol=1e-8, device=False):
+        """BAProblem.covariance of every problem, one after the other (a host
+        loop: not a per-iteration path); a list, one entry per problem."""
+        return [p.covariance(cameras, pairs, scale, rank_tol, device) for p in self.problems]
 
 
 # ----------------------------------------------------------------------------- kernels
