@@ -168,6 +168,22 @@ int slam_pnp_ransac(const double* d_Q, const double* d_q, const int32_t* d_count
  * fewer than this many doubles (ws_len) returns SLAM_ERR_WORKSPACE.  The
  * workspace is the caller's: calls that may overlap (other streams) need their own. */
 long long slam_pnp_workspace_len(int batch, int n_hyp);
+/* slam_pnp_ransac with a caller-owned EPnP scratch d_scratch of scratch_len
+ * doubles (what the eigen kernel of a hypothesis hands to its beta kernel): the
+ * form for a hot loop.  Same results bit for bit.  A scratch_len below
+ * slam_pnp_scratch_len(batch, n_hyp) returns SLAM_ERR_WORKSPACE with a message
+ * naming the needed length, before any GPU call.  The scratch is the caller's:
+ * calls that may overlap (other streams) need their own; it need not be cleared
+ * between calls.  slam_pnp_ransac itself takes its scratch from the stream's
+ * memory pool (hipMallocAsync / hipFreeAsync on `stream`). */
+int slam_pnp_ransac_ws(const double* d_Q, const double* d_q, const int32_t* d_count, int cap,
+                       int batch, const double* d_K, uint64_t seed, int item0, int n_hyp,
+                       double reproj_thresh, int hyp_iters, int refine_iters, double* d_rvec,
+                       double* d_tvec, int32_t* d_ninliers, uint8_t* d_mask, double* d_ws,
+                       long long ws_len, double* d_scratch, long long scratch_len, void* stream);
+/* Doubles of slam_pnp_ransac_ws's scratch (106 per item and hypothesis);
+ * monotone in both arguments, 0 when either is <= 0. */
+long long slam_pnp_scratch_len(int batch, int n_hyp);
 
 /* Pose chain of main.py:94-98, 120-124 (pose_{b+1} = pose_b @ T_b with
  * T_b = [Rodrigues(-rvec_b) | -tvec_b], transformation.py:15-19; when

@@ -71,6 +71,14 @@ int main(void) {
              "pnp null workspace");
   expect_rc(slam_pnp_ransac(P, P, P, 16, 2, P, 0, 0, 64, 2.0, 10, 10, P, P, P, P, P, 767, NULL),
             SLAM_ERR_WORKSPACE, "pnp workspace too short");
+  expect_rc(slam_pnp_ransac_ws(P, P, P, 16, 2, P, 0, 0, 64, 2.0, 10, 10, P, P, P, P, P, 768, P,
+                               2 * 64 * 106 - 1, NULL),
+            SLAM_ERR_WORKSPACE, "pnp scratch too short");
+  expect_arg(slam_pnp_ransac_ws(P, P, P, 16, 2, P, 0, 0, 64, 2.0, 10, 10, P, P, P, P, P, 768, NULL,
+                                2 * 64 * 106, NULL),
+             "pnp null scratch");
+  expect(slam_pnp_scratch_len(2, 64) == 2LL * 64 * 106, "pnp scratch len");
+  expect(slam_pnp_scratch_len(1 << 20, 256) > 0, "pnp scratch len no int overflow");
   expect_arg(slam_ba_iterate_batch(NULL, 3, 1, NULL), "ba iterate_batch null array");
   expect_arg(slam_ba_reset_batch(NULL, 2, 1e-4, NULL), "ba reset_batch null array");
   expect(slam_pnp_workspace_len(4, 128) == 4LL * 128 * 6, "pnp workspace len");

@@ -13,6 +13,7 @@
 
 #include <hip/hip_runtime.h>
 #include <cmath>
+#include <cstddef>
 
 namespace slam_epnp {
 
@@ -287,30 +288,51 @@ __device__ inline void ep_rvec(const double R[9], double r[3]) {
 }
 
 // ---------------------------------------------------------------- group form
-// One EPnP per 16-lane group of a one-wave workgroup (lane k = lane & 15 of
-// group g = lane >> 4); the steps that dominate -- M^T M and its 12x12 Jacobi
-// eigen-decomposition -- run with lanes k < 12 owning row k, the three beta
-// approximations on lanes 0..2, the rest on lane 0.  Every value is computed
-// with the operations of oracle/epnp.h in the same order.  The caller's
-// workgroup is one wave, so __syncthreads() is a cheap wave-level fence.
+// One EPnP in two kernels (csrc/geometry.hip), each of one-wave workgroups.
+// Eigen kernel, a 16-lane group per hypothesis (lane k = lane & 15 of group
+// g = lane >> 4): the steps that dominate -- M^T M and its 12x12 Jacobi
+// eigen-decomposition -- run with lanes k < 12 owning row k, the sample, the
+// control points and the eigen ordering on lane 0.  Beta kernel, a 4-lane
+// group per hypothesis: L and rho on lane 0, the three beta approximations on
+// lanes 0..2, the choice on lane 0; it holds the registers of that long serial
+// chain on a quarter of the waves.  Every value is computed with the
+// operations of oracle/epnp.h in the same order.  A workgroup is one wave, so
+// __syncthreads() is a cheap wave-level fence.
 constexpr int kJld = 13;  // row stride of the Jacobi buffers (odd: rows on distinct banks)
-struct EpGroup {         // LDS of one group
+struct EpGroup {         // LDS of one group of the eigen kernel
   double A[144], V[144]; // M^T M (destroyed: eigenvalues on the diagonal), eigenvectors
   double alph[4 * EPNP_MAXN];
-  double v[4][12];
-  double L[60], rho[6];
   double cw[4][3];
-  double res[3][8];      // per approximation: err, p[6], valid
   double offdia[2];
   double B[2][12 * kJld];  // Jacobi: A ping-pong (round r reads B[cur], writes B[cur ^ 1])
   double cs[12];           // Jacobi: the round's (c, s) of the 6 pairs
   double part[24];         // Jacobi: per-row diagonal / off-diagonal squares
-  double pad[27];
+  double pad[3];
+  int o12[4];            // columns of V of the 4 smallest eigenvalues, ascending
   int flag;              // 0: degenerate, 1: ok; Jacobi: 1 while sweeping
 };
 // consecutive groups 32 banks apart, so lanes 0..15 and 16..31 of a wave
 // (one ds_read_b64 bank group) never collide on the stride-13 rows
 static_assert(sizeof(EpGroup) % 256 == 128, "EpGroup stride must be 128 mod 256 bytes");
+
+// What the eigen kernel hands to the beta kernel, per hypothesis, through
+// global memory (kEpRec doubles: flag .. v), and the beta kernel's LDS of one
+// hypothesis (the record, then L, rho and the three approximations' results).
+struct EpBeta {
+  double flag;           // 0: degenerate sample (nothing else of the record is valid)
+  double pw[3 * 5], uv[2 * 5];  // the 5-point sample, draw order
+  double alph[4 * 5];
+  double cw[4][3];
+  double v[4][12];
+  double L[60], rho[6];
+  double res[3][8];      // per approximation: err, p[6], valid
+};
+constexpr int kEpRec = 1 + 15 + 10 + 20 + 12 + 48;
+static_assert(offsetof(EpBeta, L) == kEpRec * sizeof(double), "EpBeta starts with the record");
+// the lanes of a hypothesis read one address (a broadcast), the 8 hypotheses of
+// a 32-lane half read addresses one EpBeta apart: 4 mod 8 doubles puts them on
+// bank pairs 0, 4, .., 28 (ds_read_b64: a double on bank pair = its index mod 32)
+static_assert(sizeof(EpBeta) % 64 == 32, "EpBeta stride must be 4 mod 8 doubles");
 
 // control points and barycentric weights (lane 0); returns 0 when degenerate
 template <int n>
@@ -565,8 +587,9 @@ __device__ __forceinline__ void ep_jacobi12_group(EpGroup& G, int k, bool live) 
   __syncthreads();
 }
 
-// eigen ordering, the 4 null vectors, L and rho (lane 0)
-__device__ __forceinline__ void ep_lrho(EpGroup& G) {
+// eigen ordering (lane 0 of the eigen kernel): the columns of V of the 4
+// smallest eigenvalues -> G.o12
+__device__ __forceinline__ void ep_order(EpGroup& G) {
   int o12[12];
   for (int i = 0; i < 12; ++i) o12[i] = i;
   for (int i = 0; i < 4; ++i)
@@ -574,8 +597,12 @@ __device__ __forceinline__ void ep_lrho(EpGroup& G) {
       if (G.A[13 * o12[j]] < G.A[13 * o12[i]]) {
         const int tmp = o12[i]; o12[i] = o12[j]; o12[j] = tmp;
       }
-  for (int k = 0; k < 4; ++k)
-    for (int r = 0; r < 12; ++r) G.v[k][r] = G.V[12 * r + o12[k]];
+  for (int k = 0; k < 4; ++k) G.o12[k] = o12[k];
+}
+
+// L and rho from the 4 null vectors and the control points (lane 0 of the
+// beta kernel)
+__device__ __forceinline__ void ep_lrho(EpBeta& G) {
   const int pa[6] = {0, 0, 0, 1, 1, 2}, pb[6] = {1, 2, 3, 2, 3, 3};
   for (int j = 0; j < 6; ++j) {
     double dv[4][3];
@@ -606,7 +633,7 @@ __device__ __forceinline__ void ep_lrho(EpGroup& G) {
 // reprojection error -> G.res[approx] (lane `approx`)
 template <int n>
 __device__ __forceinline__ void ep_approx(int approx, const double* pw, const double* uv, double fx,
-                                          double fy, double cx, double cy, EpGroup& G) {
+                                          double fy, double cx, double cy, EpBeta& G) {
   double* res = G.res[approx];
   res[7] = 0.0;
   // columns of L per approximation: {B11 B12 B13 B14}, {B11 B12 B22},
@@ -681,7 +708,7 @@ __device__ __forceinline__ void ep_approx(int approx, const double* pw, const do
 }
 
 // the choice of epnp(): least error, first on ties, then the finiteness check
-__device__ __forceinline__ int ep_choose(const EpGroup& G, double p[6]) {
+__device__ __forceinline__ int ep_choose(const EpBeta& G, double p[6]) {
   double best_err = INFINITY;
   int ok = 0;
   for (int a = 0; a < 3; ++a) {

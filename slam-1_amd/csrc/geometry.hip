@@ -9,6 +9,9 @@
 // RANSAC sampling is a counter-based splitmix64 stream keyed by (seed, frame,
 // hypothesis) so the CPU oracle draws the same subsets (OpenCV's own RNG
 // sequence is not reproducible here).
+// PnP kernels, in launch order: k_pnp_hyp_eig (sample, control points, M^T M,
+// 12x12 Jacobi -> EPnP scratch), k_pnp_hyp_beta (betas, pose choice -> ws),
+// k_pnp_hyp_lm (sample LM on ws), k_pnp (scoring, selection, refinement).
 #include "common.hpp"
 #include "epnp.hpp"
 #include "dlt.hpp"
@@ -356,16 +359,28 @@ __device__ __forceinline__ void wave_allsum32(double (&v)[32]) {
   for (int j = 0; j < 32; ++j) v[j] = readlane_d(tot, 2 * j);
 }
 
-// PnP-RANSAC hypotheses: kHypGroups per one-wave workgroup, a 16-lane group
-// each.  Sample h of pair b: 5 distinct indices from splitmix64(seed,
-// item0 + b, h); EPnP on the sample (OpenCV's RANSAC kernel for
-// SOLVEPNP_ITERATIVE; csrc/epnp.hpp group form: M^T M rows and the 12x12
-// Jacobi on 12 lanes, the three beta approximations on 3 lanes), then
-// hyp_iters LM steps on the same 5 points from that pose (a degenerate sample
-// starts LM at r = t = 0).  Poses -> ws [b][h][6].
-constexpr int kHypGroups = 4;  // hypotheses per one-wave workgroup (16 lanes each)
+// PnP-RANSAC hypotheses.  Sample h of pair b: 5 distinct indices from
+// splitmix64(seed, item0 + b, h); EPnP on the sample (OpenCV's RANSAC kernel
+// for SOLVEPNP_ITERATIVE; csrc/epnp.hpp), then hyp_iters LM steps on the same
+// 5 points from that pose (a degenerate sample starts LM at r = t = 0).
+// Poses -> ws [b][h][6].  Three kernels of one-wave workgroups, each holding
+// only the registers of its own phase beside ORB's workgroups:
+//   k_pnp_hyp_eig   kHypGroups hypotheses a wave, 16 lanes each: sample,
+//                   control points, M^T M rows and the 12x12 Jacobi on 12
+//                   lanes, the 4 smallest eigenvectors -> a record of kEpRec
+//                   doubles per hypothesis in the scratch buffer;
+//   k_pnp_hyp_beta  kBetaGroups hypotheses a wave, 4 lanes each: L and rho,
+//                   the three beta approximations on 3 lanes (the long serial
+//                   chain, a quarter of the waves), the choice -> ws;
+//   k_pnp_hyp_lm    kHypGroups hypotheses a wave, 16 lanes each: the sample LM.
+constexpr int kHypGroups = 4;    // k_pnp_hyp_eig: hypotheses per workgroup (16 lanes each)
+constexpr int kBetaGroups = 16;  // k_pnp_hyp_beta: hypotheses per workgroup (4 lanes each)
+constexpr int kEpRec = slam_epnp::kEpRec;
 #ifdef SLAM_PNPH_TRACE
-__device__ unsigned long long g_pnph[8];
+// [0..5): k_pnp_hyp_eig (start, sample + control points, M^T M, Jacobi, ordering
+// + record), [7]: its Jacobi sweeps; [8..13): k_pnp_hyp_beta (start, record in
+// LDS, L + rho, approximations, choice written)
+__device__ unsigned long long g_pnph[16];
 #define PNPH_T(i) do { if (threadIdx.x == 0 && blockIdx.x == 3 && blockIdx.y == 5) g_pnph[i] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
 #define PNPH_T(i) (void)0
@@ -392,11 +407,15 @@ __device__ void pnp_sample(uint64_t seed, int item, int h, int L, const double* 
   }
 }
 
-__global__ __launch_bounds__(64) void k_pnp_hyp(const double* __restrict__ Qall,
-                                                const double* __restrict__ qall,
-                                                const int32_t* __restrict__ count, int cap,
-                                                const double* __restrict__ Kp, uint64_t seed,
-                                                int item0, int n_hyp, double* __restrict__ ws) {
+// scr [b][h][kEpRec]: flag, pw (15), uv (10), alph (20), cw (12), v (4 x 12) --
+// the head of slam_epnp::EpBeta.  A dead group (h >= n_hyp) writes nothing; of
+// a degenerate sample only the flag (0) means anything.
+__global__ __launch_bounds__(64) void k_pnp_hyp_eig(const double* __restrict__ Qall,
+                                                    const double* __restrict__ qall,
+                                                    const int32_t* __restrict__ count, int cap,
+                                                    const double* __restrict__ Kp, uint64_t seed,
+                                                    int item0, int n_hyp,
+                                                    double* __restrict__ scr) {
 #ifdef SLAM_PNP_PRIO
   __builtin_amdgcn_s_setprio(SLAM_PNP_PRIO);
 #endif
@@ -429,12 +448,59 @@ __global__ __launch_bounds__(64) void k_pnp_hyp(const double* __restrict__ Qall,
 #ifdef SLAM_PNPH_TRACE
   if (threadIdx.x == 0 && blockIdx.x == 3 && blockIdx.y == 5) g_pnph[7] = (unsigned long long)G.offdia[1];
 #endif
+  if (ok && k == 0) slam_epnp::ep_order(G);
+  __syncthreads();
+  if (live) {
+    double* rec = scr + ((size_t)b * n_hyp + h) * kEpRec;
+    if (k == 0) rec[0] = ok ? 1.0 : 0.0;
+    if (ok) {
+      if (k < 3 * kMinSample) rec[1 + k] = spw[g][k];
+      if (k < 2 * kMinSample) rec[16 + k] = suv[g][k];
+      for (int i = k; i < 4 * kMinSample; i += 16) rec[26 + i] = G.alph[i];
+      if (k < 12) {
+        rec[46 + k] = G.cw[k / 3][k % 3];
+        // row k of the 4 null vectors: v[kk][k] = V[k][o12[kk]]
+        for (int kk = 0; kk < 4; ++kk) rec[58 + 12 * kk + k] = G.V[12 * k + G.o12[kk]];
+      }
+    }
+  }
+  PNPH_T(4);
+}
+
+__global__ __launch_bounds__(64) void k_pnp_hyp_beta(const int32_t* __restrict__ count, int cap,
+                                                     const double* __restrict__ Kp, int n_hyp,
+                                                     const double* __restrict__ scr,
+                                                     double* __restrict__ ws) {
+#ifdef SLAM_PNP_PRIO
+  __builtin_amdgcn_s_setprio(SLAM_PNP_PRIO);
+#endif
+  __shared__ slam_epnp::EpBeta grp[kBetaGroups];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const int g = t >> 2, k = t & 3;
+  const int h0 = blockIdx.y * kBetaGroups, h = h0 + g;
+  const int L = min(max(count[b], 0), cap);
+  if (L < kMinSample) return;  // uniform over the workgroup
+  const bool live = h < n_hyp;
+  const Cam K{Kp[0], Kp[4], Kp[2], Kp[5]};
+  slam_epnp::EpBeta& G = grp[g];
+  PNPH_T(8);
+  {  // the workgroup's records are contiguous in scr: one coalesced pass
+    const double* src = scr + ((size_t)b * n_hyp + h0) * kEpRec;
+    const int nrec = min(kBetaGroups, n_hyp - h0) * kEpRec;
+    for (int i = t; i < nrec; i += 64) {
+      const int gi = i / kEpRec;
+      reinterpret_cast<double*>(&grp[gi])[i - gi * kEpRec] = src[i];
+    }
+  }
+  __syncthreads();
+  PNPH_T(9);
+  const bool ok = live && G.flag != 0.0;
   if (ok && k == 0) slam_epnp::ep_lrho(G);
   __syncthreads();
-  PNPH_T(4);
-  if (ok && k < 3) slam_epnp::ep_approx<kMinSample>(k, spw[g], suv[g], K.fx, K.fy, K.cx, K.cy, G);
+  PNPH_T(10);
+  if (ok && k < 3) slam_epnp::ep_approx<kMinSample>(k, G.pw, G.uv, K.fx, K.fy, K.cx, K.cy, G);
   __syncthreads();
-  PNPH_T(5);
+  PNPH_T(11);
   if (k == 0 && live) {  // the EPnP pose (a degenerate sample: r = t = 0) -> ws
     double p[6] = {0, 0, 0, 0, 0, 0};
     if (!(ok && slam_epnp::ep_choose(G, p)))
@@ -442,11 +508,10 @@ __global__ __launch_bounds__(64) void k_pnp_hyp(const double* __restrict__ Qall,
     double* o = ws + ((size_t)b * n_hyp + h) * 6;
     for (int i = 0; i < 6; ++i) o[i] = p[i];
   }
-  PNPH_T(6);
+  PNPH_T(12);
 }
 
-// Hypothesis LM (the second half of a hypothesis, split from k_pnp_hyp so each
-// kernel fits beside ORB's workgroups): hyp_iters LM steps on the same 5
+// Hypothesis LM (the second half of a hypothesis): hyp_iters LM steps on the same 5
 // points from the EPnP pose in ws, the result written back in place.  The
 // sample is redrawn (same splitmix64 stream) into LDS.  A dead group
 // (h >= n_hyp) runs along on zeros and writes nothing.
@@ -534,7 +599,7 @@ __global__ __launch_bounds__(kPnPWG) void k_pnp(const double* __restrict__ Qall,
 #ifdef SLAM_PNP_PROFILE
   const uint64_t pt0 = __builtin_amdgcn_s_memtime();
 #endif
-  // ---- hypotheses (k_pnp_hyp: EPnP + LM on each sample)
+  // ---- hypotheses (k_pnp_hyp_eig, _beta, _lm: EPnP + LM on each sample)
   for (int h = t; h < n_hyp; h += kPnPWG) {
     double p[6], R[9];
     const double* src = hws + ((size_t)b * n_hyp + h) * 6;
@@ -1169,11 +1234,12 @@ extern "C" long long slam_pnp_workspace_len(int batch, int n_hyp) {
   return (long long)batch * n_hyp * 6;
 }
 
-extern "C" int slam_pnp_ransac(const double* d_Q, const double* d_q, const int32_t* d_count,
-                               int cap, int batch, const double* d_K, uint64_t seed, int item0,
-                               int n_hyp, double reproj_thresh, int hyp_iters, int refine_iters,
-                               double* d_rvec, double* d_tvec, int32_t* d_ninliers,
-                               uint8_t* d_mask, double* d_ws, long long ws_len, void* stream) {
+// the argument checks both slam_pnp_ransac entry points share (before any GPU call)
+static int pnp_check_args(const double* d_Q, const double* d_q, const int32_t* d_count, int cap,
+                          int batch, const double* d_K, int n_hyp, double reproj_thresh,
+                          int hyp_iters, int refine_iters, const double* d_rvec,
+                          const double* d_tvec, const int32_t* d_ninliers, const uint8_t* d_mask,
+                          const double* d_ws, long long ws_len) {
   SLAM_REQUIRE(batch >= 0 && cap >= 0, "slam_pnp_ransac: bad shape");
   SLAM_REQUIRE(n_hyp >= 1 && n_hyp <= kMaxHyp, "slam_pnp_ransac: n_hyp in [1, %d]", kMaxHyp);
   SLAM_REQUIRE(hyp_iters >= 0 && refine_iters >= 0 && reproj_thresh > 0,
@@ -1186,11 +1252,37 @@ extern "C" int slam_pnp_ransac(const double* d_Q, const double* d_q, const int32
                     slam_pnp_workspace_len(batch, n_hyp));
     return SLAM_ERR_WORKSPACE;
   }
+  return SLAM_OK;
+}
+
+extern "C" long long slam_pnp_scratch_len(int batch, int n_hyp) {
+  return (long long)(batch > 0 ? batch : 0) * (n_hyp > 0 ? n_hyp : 0) * kEpRec;
+}
+
+extern "C" int slam_pnp_ransac_ws(const double* d_Q, const double* d_q, const int32_t* d_count,
+                                  int cap, int batch, const double* d_K, uint64_t seed, int item0,
+                                  int n_hyp, double reproj_thresh, int hyp_iters, int refine_iters,
+                                  double* d_rvec, double* d_tvec, int32_t* d_ninliers,
+                                  uint8_t* d_mask, double* d_ws, long long ws_len,
+                                  double* d_scratch, long long scratch_len, void* stream) {
+  if (int rc = pnp_check_args(d_Q, d_q, d_count, cap, batch, d_K, n_hyp, reproj_thresh, hyp_iters,
+                              refine_iters, d_rvec, d_tvec, d_ninliers, d_mask, d_ws, ws_len))
+    return rc;
+  if (batch == 0) return SLAM_OK;
+  SLAM_REQUIRE(d_scratch != nullptr, "slam_pnp_ransac: null scratch");
+  if (scratch_len < slam_pnp_scratch_len(batch, n_hyp)) {
+    slam::set_error("slam_pnp_ransac: scratch %lld < %lld doubles", scratch_len,
+                    slam_pnp_scratch_len(batch, n_hyp));
+    return SLAM_ERR_WORKSPACE;
+  }
   hipStream_t s = slam::as_stream(stream);
-  const dim3 hgrid(batch, (n_hyp + kHypGroups - 1) / kHypGroups);
-  k_pnp_hyp<<<hgrid, 64, 0, s>>>(d_Q, d_q, d_count, cap, d_K, seed, item0, n_hyp, d_ws);
-  SLAM_LAUNCHED("k_pnp_hyp");
-  k_pnp_hyp_lm<<<hgrid, 64, 0, s>>>(d_Q, d_q, d_count, cap, d_K, seed, item0, n_hyp, hyp_iters,
+  const dim3 egrid(batch, (n_hyp + kHypGroups - 1) / kHypGroups);
+  k_pnp_hyp_eig<<<egrid, 64, 0, s>>>(d_Q, d_q, d_count, cap, d_K, seed, item0, n_hyp, d_scratch);
+  SLAM_LAUNCHED("k_pnp_hyp_eig");
+  const dim3 bgrid(batch, (n_hyp + kBetaGroups - 1) / kBetaGroups);
+  k_pnp_hyp_beta<<<bgrid, 64, 0, s>>>(d_count, cap, d_K, n_hyp, d_scratch, d_ws);
+  SLAM_LAUNCHED("k_pnp_hyp_beta");
+  k_pnp_hyp_lm<<<egrid, 64, 0, s>>>(d_Q, d_q, d_count, cap, d_K, seed, item0, n_hyp, hyp_iters,
                                     d_ws);
   SLAM_LAUNCHED("k_pnp_hyp_lm");
   k_pnp<<<batch, kPnPWG, 0, s>>>(d_Q, d_q, d_count, cap, d_K, seed, item0, n_hyp, reproj_thresh,
@@ -1198,6 +1290,28 @@ extern "C" int slam_pnp_ransac(const double* d_Q, const double* d_q, const int32
                                  d_ws);
   SLAM_LAUNCHED("k_pnp");
   return SLAM_OK;
+}
+
+// The same kernels with the EPnP scratch taken from, and returned to, the
+// stream's memory pool (stream-ordered: no synchronisation).
+extern "C" int slam_pnp_ransac(const double* d_Q, const double* d_q, const int32_t* d_count,
+                               int cap, int batch, const double* d_K, uint64_t seed, int item0,
+                               int n_hyp, double reproj_thresh, int hyp_iters, int refine_iters,
+                               double* d_rvec, double* d_tvec, int32_t* d_ninliers,
+                               uint8_t* d_mask, double* d_ws, long long ws_len, void* stream) {
+  if (int rc = pnp_check_args(d_Q, d_q, d_count, cap, batch, d_K, n_hyp, reproj_thresh, hyp_iters,
+                              refine_iters, d_rvec, d_tvec, d_ninliers, d_mask, d_ws, ws_len))
+    return rc;
+  if (batch == 0) return SLAM_OK;
+  hipStream_t s = slam::as_stream(stream);
+  const long long n = slam_pnp_scratch_len(batch, n_hyp);
+  double* scr = nullptr;
+  SLAM_HIP(hipMallocAsync(reinterpret_cast<void**>(&scr), (size_t)n * sizeof(double), s));
+  const int rc = slam_pnp_ransac_ws(d_Q, d_q, d_count, cap, batch, d_K, seed, item0, n_hyp,
+                                    reproj_thresh, hyp_iters, refine_iters, d_rvec, d_tvec,
+                                    d_ninliers, d_mask, d_ws, ws_len, scr, n, s);
+  SLAM_HIP(hipFreeAsync(scr, s));
+  return rc;
 }
 
 extern "C" int slam_vo_pose_workspace_bytes(int batch, int max_iter, size_t* bytes) {
@@ -1273,7 +1387,7 @@ extern "C" int slam_pose_chain(const double* d_rvec, const double* d_tvec,
 #ifdef SLAM_PNPH_TRACE
 extern "C" int slam_pnph_trace(unsigned long long* out) {
   SLAM_HIP(hipDeviceSynchronize());
-  SLAM_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pnph), 8 * sizeof(unsigned long long)));
+  SLAM_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pnph), 16 * sizeof(unsigned long long)));
   return SLAM_OK;
 }
 #endif

@@ -81,6 +81,9 @@ SIGNATURES = {
     "slam_pnp_ransac": [c_p, c_p, c_p, c_int, c_int, c_p, c_uint64, c_int, c_int, c_double, c_int,
                         c_int, c_p, c_p, c_p, c_p, c_p, c_longlong, c_p],
     "slam_pnp_workspace_len": [c_int, c_int],
+    "slam_pnp_ransac_ws": [c_p, c_p, c_p, c_int, c_int, c_p, c_uint64, c_int, c_int, c_double,
+                           c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_longlong, c_p, c_longlong, c_p],
+    "slam_pnp_scratch_len": [c_int, c_int],
     "slam_pose_chain": [c_p, c_p, c_p, c_int, c_p, c_p, c_p],
     "slam_vo_estimate_pose": [c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_p, c_uint64, c_int, c_int,
                               c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_size_t, c_p],
@@ -158,6 +161,7 @@ _RESTYPE = {"slam_last_error": ctypes.c_char_p, "slam_ba_sys_len": ctypes.c_long
             "slam_ba_plan_bound": ctypes.c_longlong,
             "slam_ba_chol_len": ctypes.c_longlong, "slam_ba_cov_workspace_len": ctypes.c_longlong,
             "slam_pnp_workspace_len": ctypes.c_longlong,
+            "slam_pnp_scratch_len": ctypes.c_longlong,
             "slam_fundamental_workspace_len": ctypes.c_longlong,
             "slam_pose_chain_workspace_len": ctypes.c_longlong}
 

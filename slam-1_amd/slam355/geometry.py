@@ -103,12 +103,15 @@ def triangulate(ptl, ptr_, count, P_l, P_r, out=None, stream=None):
     return X
 
 
-def pnp_ransac(Q, q, count, K, seed=0, item0=0, out=None, stream=None, ws=None, **kw):
+def pnp_ransac(Q, q, count, K, seed=0, item0=0, out=None, stream=None, ws=None, scratch=None,
+               **kw):
     """Q [B,cap,3], q [B,cap,2] f64 -> (rvec [B,3], tvec [B,3], ninliers [B], mask [B,cap]).
 
     ws: the hypothesis-pose workspace (pnp_workspace(B, n_hyp)); calls that may
     run concurrently (other streams) must each pass their own.  Without one, a
-    fresh buffer is allocated for this call (and kept alive for `stream`)."""
+    fresh buffer is allocated for this call (and kept alive for `stream`).
+    scratch: the EPnP scratch (pnp_scratch(B, n_hyp)), the caller's in the same
+    way.  Without one, the library takes a stream-ordered buffer for this call."""
     prm = dict(PNP_DEFAULTS, **kw)
     B, cap, _ = Q.shape
     dev = Q.device
@@ -124,16 +127,26 @@ def pnp_ransac(Q, q, count, K, seed=0, item0=0, out=None, stream=None, ws=None, 
         ws = pnp_workspace(B, prm["n_hyp"], dev)
         if stream is not None and stream != torch.cuda.current_stream(dev):
             ws.record_stream(stream)  # freed by the caching allocator only after `stream`
-    _lib.call("slam_pnp_ransac", ptr(Q), ptr(q), ptr(count), cap, B, ptr(Kt.contiguous()),
-              int(seed) & ((1 << 64) - 1), int(item0), prm["n_hyp"], float(prm["reproj_thresh"]),
-              prm["hyp_iters"], prm["refine_iters"], ptr(rvec), ptr(tvec), ptr(ninl), ptr(mask),
-              ptr(ws), ws.numel(), stream_ptr(stream))
+    args = (ptr(Q), ptr(q), ptr(count), cap, B, ptr(Kt.contiguous()),
+            int(seed) & ((1 << 64) - 1), int(item0), prm["n_hyp"], float(prm["reproj_thresh"]),
+            prm["hyp_iters"], prm["refine_iters"], ptr(rvec), ptr(tvec), ptr(ninl), ptr(mask),
+            ptr(ws), ws.numel())
+    if scratch is None:
+        _lib.call("slam_pnp_ransac", *args, stream_ptr(stream))
+    else:
+        _lib.call("slam_pnp_ransac_ws", *args, ptr(scratch), scratch.numel(), stream_ptr(stream))
     return rvec, tvec, ninl, mask
 
 
 def pnp_workspace(B, n_hyp=PNP_DEFAULTS["n_hyp"], dev="cuda"):
     """Hypothesis-pose workspace of slam_pnp_ransac for B items (f64)."""
     n = int(_lib.lib.slam_pnp_workspace_len(B, n_hyp))
+    return torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+
+
+def pnp_scratch(B, n_hyp=PNP_DEFAULTS["n_hyp"], dev="cuda"):
+    """EPnP scratch of slam_pnp_ransac_ws for B items (f64)."""
+    n = int(_lib.lib.slam_pnp_scratch_len(B, n_hyp))
     return torch.empty(max(n, 1), dtype=torch.float64, device=dev)
 
 

@@ -86,6 +86,7 @@ class Tracker:
         self.p_ninl = torch.zeros((B,), **i32)
         self.p_mask = torch.zeros((B, cap), **u8)
         self.p_ws = geometry.pnp_workspace(B, dev=d)  # this Tracker's PnP hypotheses
+        self.p_scr = geometry.pnp_scratch(B, dev=d)  # and their EPnP scratch
         self.f_ws = geometry.fundamental_workspace(B, dev=d)  # and its F-LMedS candidates
         self.imgs = torch.zeros((2 * B + 1, H, W), **u8)
         # device pose chain (main.py:120-124): (pose, T) carried across batches
@@ -200,7 +201,7 @@ class Tracker:
         # PnP-RANSAC (transformation.py:11-13)
         geometry.pnp_ransac(self.Q1, self.q2, self.t_cnt, self.tK, seed=self.seed, item0=frame0,
                             out=(self.rvec, self.tvec, self.p_ninl, self.p_mask), stream=st,
-                            ws=self.p_ws)
+                            ws=self.p_ws, scratch=self.p_scr)
         mark("pnp")
         h0 = self._ht("pnp_launch", h0)
         if chain:
