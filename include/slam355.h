@@ -471,7 +471,7 @@ int slam_ba_problem_size(void);
 
 /* Problems per batched launch (slam_ba_iterate_batch splits larger batches).
  * The descriptors travel by value in the kernel arguments: 16 x 408 B
- * (ba.hip static_asserts the size; ROCm 7.2 takes this > 4 KB argument
+ * (ba_common.hpp static_asserts the size; ROCm 7.2 takes this > 4 KB argument
  * segment, exercised by tests/test_ba.py's 16-window launch). */
 #ifndef SLAM_BA_MAX_BATCH
 #define SLAM_BA_MAX_BATCH 16

@@ -1,7 +1,7 @@
 """Per-panel timeline of k_solve_blk (wave 0 of window 0, s_memtime stamps) from a
 library built with -DSLAM_SOLVE_TRACE:
 
-    scripts/build_variant.sh strace ba.hip -DSLAM_SOLVE_TRACE
+    scripts/build_variant.sh strace ba_solve.hip -DSLAM_SOLVE_TRACE
     python scripts/solve_trace.py [LIB_NAME] [N_WINDOWS]
 
 Stamp slots per panel: 0 panel start, 2 factor done, 3 after the W/L barrier,

@@ -5,7 +5,11 @@
 // and scipy least_squares TRF) with LM on the normal equations, all state on
 // the device so a fixed number of iterations runs with no host round trip.
 //
-// One LM iteration = 4 launches (local BA):
+// One LM iteration = 4 launches (local BA); k_solve_blk is in
+// ba_solve.hip, every other kernel in this file.  Shared: ba_common.hpp (batch
+// descriptor, solver-side helpers, the host functions that cross the files),
+// ba_layout.hpp, ba_project.hpp (cam_prep), ba_epilogue.hpp (solve epilogue),
+// dpp_fmac.hpp (fused DPP broadcast FMAs).
 //   k_linearize     point group -> residuals + Jacobians, V*_p, e_p = V*^-1 g_p,
 //                                  W_o = Jc^T Jp, u_o = Jp e_p, and the group's
 //                                  slot partials of the reduced camera system:
@@ -14,20 +18,22 @@
 //   k_assemble      block  -> S = sum of its slot partials in group order,
 //                             b = -Jc^T r - Jc^T u, g, diag U, cost
 //   (all-reduce of sys over ranks happens here for multi-GPU)
-//   k_solve_blk     1 WG   -> damp, blocked LDL^T (MFMA trailing updates), camera
+//   k_solve_blk     1 WG   -> damp, blocked LDL^T (MFMA trailing updates), camera  [ba_solve.hip]
 //                             step, pred_cam, trial cameras (tiled k_tl3_flow / k_tl2_* for 9C > 120)
 //   k_back_trial    point group -> point step, trial points, trial |r|^2 and
 //                                  pred partials; the last group sums them into
 //                                  small (and, single rank, decides)
 //   (all-reduce of small over ranks, then k_decide)
 //   k_decide        1 lane -> rho, accept/reject, lambda update, buffer swap
-#include "common.hpp"
+#include "ba_common.hpp"
+#include "ba_epilogue.hpp"
+#include "ba_layout.hpp"
+#include "ba_project.hpp"
+#include "dpp_fmac.hpp"
 
-#include <cmath>
+using slam::Launch;
 
 namespace {
-
-typedef double d4 __attribute__((ext_vector_type(4)));
 
 // Cross-workgroup hand-off inside one launch (ticket pattern): the partials
 // are stored and loaded with agent-scope relaxed atomics, i.e. write-through
@@ -47,19 +53,9 @@ __device__ __forceinline__ void ticket_reset(uint32_t* p) {
 }
 
 constexpr double kClamp = 5000.0;
-constexpr double kDiagMin = 1e-6, kDiagMax = 1e32;
 constexpr double kLamMin = 1e-16, kLamMax = 1e32;
 constexpr int kBS = 256;   // block size of the element-wise kernels
 
-// Batched LM: independent problems (local-BA windows) advance through one set
-// of launches, one problem per blockIdx.y; each keeps its own buffers and LM
-// state, so the iterates of a batched problem equal its solo iterates.  The
-// problem descriptors travel by value in the kernel arguments (16 x 408 B).
-constexpr int kBaMaxBatch = SLAM_BA_MAX_BATCH;
-struct BaBatch {
-  slam_ba_problem p[kBaMaxBatch];
-};
-#define BA_PROB(b) const slam_ba_problem& p = (b).p[blockIdx.y]
 // The batched per-observation / per-block launches (grid x = the problem's
 // workgroups, y = problem) with 8k problems: workgroups are dealt round-robin
 // over the 8 XCDs (for speed only; nothing depends on it), so the linear
@@ -82,63 +78,7 @@ __device__ __forceinline__ int2 ba_xcd_map() {
   const int2 bw_ = ba_xcd_map();     \
   const int bx = bw_.x;              \
   const slam_ba_problem& p = (b).p[bw_.y]
-// the batch travels by value in the kernel arguments: 16 x 408 B,
-// beyond the traditional 4 KB; ROCm 7.2 takes it (tests/test_ba.py launches 16)
-static_assert(sizeof(slam_ba_problem) == 408, "slam_ba_problem grew: re-check the kernarg size");
-static_assert(sizeof(BaBatch) <= 16 * 408, "BaBatch kernel argument size");
-
-// The LM kernels are short and latency-bound and usually share their CUs with
-// the (throughput-bound) ORB workgroups of the concurrent tracking stream: they
-// raise their waves' issue priority so their dependent chains are issued first
-// and the ORB waves fill the gaps.
-__device__ __forceinline__ void lm_wave_priority() { __builtin_amdgcn_s_setprio(3); }
-
 // ---------------------------------------------------------------- projection
-// Residual (proj - q) of BundleAdjustment.py:317-337 with the operation order
-// of the numpy code, and optionally its analytic 2x12 Jacobian.
-// Per-camera part of the projection: everything that depends on the rotation
-// vector only (theta, v, cos, sin, R and the Jacobian's A matrix), computed
-// once per camera by cam_prep and stored as a 32-double record; the per-
-// observation part (reproject_pre) then does no sqrt/sin/cos/division by theta.
-// Both halves keep the operation order of the single-function form, so
-// results are bit-identical to computing everything per observation.
-constexpr int kCamRec = 32;  // c s omc v(3) R(9) A(9) inv small t(3) f k1 k2 pad(0)
-__device__ __forceinline__ void cam_prep(const double* __restrict__ cam, double* __restrict__ o) {
-  const double w0 = cam[0], w1 = cam[1], w2 = cam[2];
-  const double th = sqrt(w0 * w0 + w1 * w1 + w2 * w2);
-  double v0 = 0.0, v1 = 0.0, v2 = 0.0;  // nan_to_num(w / 0) == 0  (:292-293)
-  if (th > 0.0) {
-    v0 = w0 / th;
-    v1 = w1 / th;
-    v2 = w2 / th;
-  }
-  const double c = cos(th), s = sin(th);
-  const double omc = 1.0 - c;
-  // R = c I + s [v]x + (1-c) v v^T
-  double R[3][3];
-  R[0][0] = c + omc * v0 * v0; R[0][1] = -s * v2 + omc * v0 * v1; R[0][2] = s * v1 + omc * v0 * v2;
-  R[1][0] = s * v2 + omc * v1 * v0; R[1][1] = c + omc * v1 * v1; R[1][2] = -s * v0 + omc * v1 * v2;
-  R[2][0] = -s * v1 + omc * v2 * v0; R[2][1] = s * v0 + omc * v2 * v1; R[2][2] = c + omc * v2 * v2;
-  // dRX/dw (Gallego & Yezzi): -R [X]x A / |w|^2 with A = w w^T + (R^T - I)[w]x
-  const double th2 = w0 * w0 + w1 * w1 + w2 * w2;
-  const double W[3][3] = {{0.0, -w2, w1}, {w2, 0.0, -w0}, {-w1, w0, 0.0}};
-  const double w[3] = {w0, w1, w2};
-  double A[3][3];
-  for (int i = 0; i < 3; ++i)
-    for (int k = 0; k < 3; ++k) {
-      double acc = w[i] * w[k];
-      for (int j = 0; j < 3; ++j) acc += R[j][i] * W[j][k];
-      A[i][k] = acc - W[i][k];
-    }
-  o[0] = c; o[1] = s; o[2] = omc;
-  o[3] = v0; o[4] = v1; o[5] = v2;
-  for (int i = 0; i < 9; ++i) o[6 + i] = R[i / 3][i % 3];
-  for (int i = 0; i < 9; ++i) o[15 + i] = A[i / 3][i % 3];
-  o[24] = th2 < 1e-24 ? 0.0 : -1.0 / th2;
-  o[25] = th2 < 1e-24 ? 1.0 : 0.0;
-  for (int i = 0; i < 6; ++i) o[26 + i] = cam[3 + i];
-}
-
 // Residual (proj - q) of BundleAdjustment.py:317-337 with the operation order
 // of the numpy code, and optionally its analytic 2x12 Jacobian, from a camera
 // record of cam_prep.
@@ -396,21 +336,6 @@ __device__ __forceinline__ void reproject_half(const double* __restrict__ cr,
   }
 }
 
-__device__ __forceinline__ double block_sum(double v, double* lds) {
-  // deterministic: fixed shuffle tree then fixed LDS order
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) lds[wid] = v;
-  __syncthreads();
-  double s = 0.0;
-  if (threadIdx.x == 0) {
-    const int nw = (blockDim.x + 63) >> 6;
-    for (int w = 0; w < nw; ++w) s += lds[w];
-  }
-  __syncthreads();
-  return s;  // valid on thread 0
-}
-
 // ---------------------------------------------------------------- standalone
 __global__ __launch_bounds__(kBS) void k_residual(const double* __restrict__ cams,
                                                   const double* __restrict__ pts,
@@ -436,22 +361,6 @@ __global__ __launch_bounds__(kBS) void k_residual(const double* __restrict__ cam
 }
 
 // ---------------------------------------------------------------- LM kernels
-__device__ __forceinline__ int cur_of(const double* state) {
-  return state[SLAM_BA_ST_CUR] != 0.0 ? 1 : 0;
-}
-
-__device__ __forceinline__ double clampd(double d) { return fmin(fmax(d, kDiagMin), kDiagMax); }
-
-// Layout of sys (the buffer all-reduced across ranks).  Dense (9C <= 120, the
-// one-workgroup solver): S [(9C)^2] row-major, all C(C+1)/2 blocks listed.
-// Packed (larger systems, tiled solver): only the listed upper blocks
-// (diagonal + camera pairs with common points), 81 doubles each, row-major
-// (rows of c1, columns of c2).  Then b, g, diag U [9C] each and cost [C].
-constexpr int kDenseMaxN = 120;
-__host__ __device__ __forceinline__ bool sys_packed(int n_cams) { return 9 * n_cams > kDenseMaxN; }
-__host__ __device__ __forceinline__ long long sys_vec_off(int n_cams, int n_blocks) {
-  return sys_packed(n_cams) ? 81ll * n_blocks : 81ll * n_cams * n_cams;
-}
 
 
 // Per point: V = sum Jp^T Jp and g = -sum Jp^T r over its observations, in
@@ -523,7 +432,6 @@ __device__ __forceinline__ double pt_comp(const double* jr, int stride, int kb, 
   return v;
 }
 
-constexpr int kCPart = 112;  // per camera slot: U - sum Y W^T (81), Jc^T r, Jc^T u, diag U (9 each), |r|^2, pad
 // Point groups: a workgroup owns the contiguous observation range of a group
 // of whole points (observations are sorted by point), at most kGrp of them.
 constexpr int kGrp = 128;
@@ -1610,541 +1518,6 @@ __global__ __launch_bounds__(kAsmWG) void k_assemble(BaBatch bat) {
   if (diag && t == 0) costc[c1] = sh[108];
 }
 
-// ---------------------------------------------------------------- solve
-// Reduced camera system S x = b, S SPD (damped).  Two solvers: k_solve_blk
-// (one workgroup, whole system in LDS/registers) for the local-BA window
-// (9C <= kLdsMaxN), and the tiled multi-workgroup Cholesky (k_tl3_flow, k_tl2_*) for
-// larger systems.
-constexpr int kLdsMaxN = kDenseMaxN;  // k_solve_blk keeps the system in LDS up to 9C = 120
-constexpr int kSolveHdr = 32;   // doubles of LDS header in k_solve_blk
-
-// Inputs of the epilogue: camera gradient, Gram diagonal, live cameras and the
-// per-camera cost partials (global memory in the tiled solves, LDS copies prefetched at
-// kernel start in k_solve_blk so their latency is off the critical path).
-struct EpiSrc {
-  const double *g, *dU, *cam, *costc;
-};
-#ifdef SLAM_FLOW_PROFILE
-// the dataflow solve's epilogue: start, x staged, pc / cost reduced, cameras prepared
-__device__ unsigned long long g_flow_epi[4];
-#endif
-
-// Shared epilogue: camera step, trial cameras, predicted reduction of the camera
-// part, LM cost at the live parameters.  GLOBAL (the tiled solves, 9C up to
-// 8192): the inputs are read from memory, so every thread issues its loads in
-// groups of 8 before using them (the per-thread order of the pc sum is the
-// same), and the per-camera cost is summed by all threads (strided, then the
-// fixed tree of block_sum2) instead of by thread 0 alone -- at C5 the serial
-// forms were ~18 dependent memory round trips per thread plus 500 dependent
-// loads and adds.
-__device__ __forceinline__ void block_sum2(double& a, double& b, double* lds) {
-  // deterministic: fixed shuffle tree then fixed LDS order (lds: 2 x 16 doubles)
-  for (int off = 32; off > 0; off >>= 1) {
-    a += __shfl_down(a, off, 64);
-    b += __shfl_down(b, off, 64);
-  }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) {
-    lds[wid] = a;
-    lds[16 + wid] = b;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int nw = (blockDim.x + 63) >> 6;
-    a = 0.0;
-    b = 0.0;
-    for (int w = 0; w < nw; ++w) {
-      a += lds[w];
-      b += lds[16 + w];
-    }
-  }
-  __syncthreads();
-}
-
-template <bool GLOBAL = false>
-__device__ void solve_epilogue(const slam_ba_problem& p, const double* x, bool ok, double* red,
-                               const EpiSrc& e, int fail_code = 1) {
-  const int C9 = 9 * p.n_cams, t = threadIdx.x;
-  double* state = p.state;
-  const double lam = state[SLAM_BA_ST_LAMBDA];
-  const int cur = cur_of(state);
-  double pc = 0.0, cost = 0.0;
-  if constexpr (GLOBAL) {
-    const int nt = blockDim.x;
-    for (int i0 = t; i0 < C9; i0 += 8 * nt) {
-      double xv[8], cv[8], uv[8], gv[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int i = min(i0 + q * nt, C9 - 1);
-        xv[q] = x[i];
-        cv[q] = e.cam[i];
-        uv[q] = e.dU[i];
-        gv[q] = e.g[i];
-      }
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int i = i0 + q * nt;
-        if (i < C9) {
-          const double d = ok ? xv[q] : 0.0;
-          p.delta_c[i] = d;
-          p.cams[1 - cur][i] = cv[q] + d;
-          pc += d * (lam * clampd(uv[q]) * d + gv[q]);
-        }
-      }
-    }
-    for (int c = t; c < p.n_cams; c += nt) cost += e.costc[c];
-    block_sum2(pc, cost, red);  // (its barriers also publish the trial cameras to the WG)
-#ifdef SLAM_FLOW_PROFILE
-    if (t == 0) g_flow_epi[2] = wall_clock64();
-#endif
-  } else {
-    for (int i = t; i < C9; i += blockDim.x) {
-      const double d = ok ? x[i] : 0.0;
-      p.delta_c[i] = d;
-      p.cams[1 - cur][i] = e.cam[i] + d;
-      pc += d * (lam * clampd(e.dU[i]) * d + e.g[i]);
-    }
-    pc = block_sum(pc, red);  // (its barriers also publish the trial cameras to the WG)
-    if (t == 0)
-      for (int c = 0; c < p.n_cams; ++c) cost += e.costc[c];
-  }
-  for (int c = t; c < p.n_cams; c += blockDim.x)
-    cam_prep(p.cams[1 - cur] + 9 * c, p.camrec[1 - cur] + kCamRec * c);
-#ifdef SLAM_FLOW_PROFILE
-  if (GLOBAL) {
-    __builtin_amdgcn_s_waitcnt(0);
-    __syncthreads();
-    if (t == 0) g_flow_epi[3] = wall_clock64();
-  }
-#endif
-  if (t == 0) {
-    state[SLAM_BA_ST_COST] = 0.5 * cost;
-    state[SLAM_BA_ST_PRED_CAM] = 0.5 * pc;
-    state[SLAM_BA_ST_CHOL_FAIL] = ok ? 0.0 : (double)fail_code;
-    if (!ok && fail_code == 2) state[SLAM_BA_ST_SOLVE_FAULT] += 1.0;
-  }
-}
-
-// -DSLAM_SOLVE_PROFILE: phase timestamps (wall_clock64, 100 MHz) of k_solve_blk
-// into the spare LM state slots 12..15 (ns): load, eliminate, back-substitute,
-// epilogue (scripts/ba_solve_prof.py reads them).
-#ifdef SLAM_SOLVE_PROFILE
-#define SOLVE_PROF_T(i) uint64_t prof_t##i = wall_clock64()
-#define SOLVE_PROF_END()                                                        \
-  do {                                                                          \
-    const uint64_t prof_e = wall_clock64();                                     \
-    if (threadIdx.x == 0) {                                                     \
-      p.state[12] = 10.0 * (double)(prof_t1 - prof_t0);                         \
-      p.state[13] = 10.0 * (double)(prof_t2 - prof_t1);                         \
-      p.state[14] = 10.0 * (double)(prof_t3 - prof_t2);                         \
-      p.state[15] = 10.0 * (double)(prof_e - prof_t3);                          \
-    }                                                                           \
-  } while (0)
-#else
-#define SOLVE_PROF_T(i) (void)0
-#define SOLVE_PROF_END() (void)0
-#endif
-
-// Small systems (9C <= kLdsMaxN, the local-BA window): blocked LDL^T with the
-// trailing updates on the f64 matrix cores.
-//
-// The augmented matrix [S ; b^T] ((n+1) x n, b carried as row n so the
-// elimination also performs the forward substitution) is kept as 16x16 f64
-// MFMA accumulator tiles, lower tiles only, spread round-robin over the 4
-// waves (<= 36 tiles for n <= 120, <= 9 per wave).  One block step per camera
-// (9 columns):
-//   (a) the owners of the 9 panel columns copy them to LDS;        barrier
-//   (b) wave 0 factors the panel in registers, two rows per lane, pivot rows
-//       broadcast with v_readlane (no LDS round trips, no barriers); it writes
-//       W = -A_panel and L = A_panel D^-1 for the rows below the panel (zeros
-//       elsewhere) and the final factor columns;                    barrier
-//   (c) every wave updates its live tiles: T -= W_I L_J^T, 3 MFMAs
-//       (v_mfma_f64_16x16x4_f64, K = 9 padded to 12) per tile.
-// 2 barriers per camera instead of one per column.  Back substitution runs in
-// wave 0 with x in registers (two rows per lane) and x_k broadcast by readlane.
-constexpr int kBlkWG = 256;   // 4 waves, one per SIMD; <= 256 registers per lane (2 waves per SIMD)
-constexpr int kBlkWaves = kBlkWG / 64;
-constexpr int kTileMax = 9;   // lower 16x16 tiles per wave: 4 * 9 >= 36
-constexpr int kPanelW = 9;    // columns per block step (one camera)
-constexpr int kWLs = 13;      // W/L row stride: K = 9 padded to 3 MFMA steps of 4 (odd: no LDS bank conflicts)
-static_assert(kLdsMaxN <= kBlkWG, "k_solve_blk prefetch assumes one element per thread");
-static_assert(kBlkWaves * kTileMax >= ((kLdsMaxN + 16) / 16) * ((kLdsMaxN + 16) / 16 + 1) / 2,
-              "kTileMax too small");
-
-// 1/d from v_rcp_f64 refined by two Newton steps (full double precision, off
-// the v_div_* sequence's long dependent chain)
-__device__ __forceinline__ double rcp_f64(double d) {
-  double r = __builtin_amdgcn_rcp(d);
-  double e = __builtin_fma(-d, r, 1.0);
-  r = __builtin_fma(r, e, r);
-  e = __builtin_fma(-d, r, 1.0);
-  return __builtin_fma(r, e, r);
-}
-
-__device__ __forceinline__ double readlane_d(double v, int lane) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, lane);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), lane);
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
-// LDS layout of k_solve_blk (doubles, after the kSolveHdr header)
-struct BlkLds {
-  int n16;        // rows rounded up to a tile multiple (>= n + 1)
-  int pn, wl, ll, lf, dd, yy, xx, ep, total;
-  __host__ __device__ explicit BlkLds(int n) {
-    n16 = ((n + 1 + 15) / 16) * 16;
-    pn = kSolveHdr;                       // [n16][kPanelW] panel copy
-    wl = pn + n16 * kPanelW;              // [n16][kWLs] W = -A_panel (rows below the panel)
-    ll = wl + n16 * kWLs;                 // [n16][kWLs] L = A_panel D^-1
-    lf = ll + n16 * kWLs;                 // [n(n-1)/2] factor L, packed by rows
-    dd = lf + ((n * (n - 1) / 2 + 1) & ~1);  // [n] D
-    yy = dd + ((n + 1) & ~1);             // [n] y = L^-1 b
-    xx = yy + ((n + 1) & ~1);             // [n] solution
-    ep = xx + ((n + 1) & ~1);             // [5][n] b, g, diagU, live cameras, cost partials
-    total = ep + 5 * ((n + 1) & ~1);
-  }
-};
-
-// -DSLAM_SOLVE_TRACE: s_memtime of problem 0's thread 0 at the points of each
-// block step (rows 0..17; 18, 19: after the loop and the load); slam_solve_trace
-// reads them (scripts/solve_trace.py).
-#ifdef SLAM_SOLVE_TRACE
-__device__ unsigned long long g_solve_trace[20][6];
-#define SOLVE_TR(step, i)                                                        \
-  do {                                                                           \
-    if (threadIdx.x == 0 && blockIdx.y == 0 && (step) < 20)                      \
-      g_solve_trace[step][i] = __builtin_amdgcn_s_memtime();                     \
-  } while (0)
-#else
-#define SOLVE_TR(step, i) (void)0
-#endif
-
-// k_solve_blk's panel pivots, the same fused form (9-wide panels):
-// u[i] += bcast_i(uj) * nl for i = J+2..8 (column J's updates after the next
-// pivot's entry, which stays in compiler code)
-template <int J> struct PanelRest;
-static_assert(kPanelW == 9, "PanelRest is written for 9-wide panels");
-template <> struct PanelRest<0> {
-  static __device__ __forceinline__ void run(double (&u)[9], double uj, double nl) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %7, %8 row_newbcast:2 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %7, %8 row_newbcast:3 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %7, %8 row_newbcast:4 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %7, %8 row_newbcast:5 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %4, %7, %8 row_newbcast:6 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %5, %7, %8 row_newbcast:7 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %6, %7, %8 row_newbcast:8 row_mask:0xf bank_mask:0xf\n"
-        : "+v"(u[2]), "+v"(u[3]), "+v"(u[4]), "+v"(u[5]), "+v"(u[6]), "+v"(u[7]), "+v"(u[8])
-        : "v"(uj), "v"(nl));
-  }
-};
-template <> struct PanelRest<1> {
-  static __device__ __forceinline__ void run(double (&u)[9], double uj, double nl) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %6, %7 row_newbcast:3 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %6, %7 row_newbcast:4 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %6, %7 row_newbcast:5 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %6, %7 row_newbcast:6 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %4, %6, %7 row_newbcast:7 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %5, %6, %7 row_newbcast:8 row_mask:0xf bank_mask:0xf\n"
-        : "+v"(u[3]), "+v"(u[4]), "+v"(u[5]), "+v"(u[6]), "+v"(u[7]), "+v"(u[8])
-        : "v"(uj), "v"(nl));
-  }
-};
-template <> struct PanelRest<2> {
-  static __device__ __forceinline__ void run(double (&u)[9], double uj, double nl) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %5, %6 row_newbcast:4 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %5, %6 row_newbcast:5 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %5, %6 row_newbcast:6 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %5, %6 row_newbcast:7 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %4, %5, %6 row_newbcast:8 row_mask:0xf bank_mask:0xf\n"
-        : "+v"(u[4]), "+v"(u[5]), "+v"(u[6]), "+v"(u[7]), "+v"(u[8])
-        : "v"(uj), "v"(nl));
-  }
-};
-template <> struct PanelRest<3> {
-  static __device__ __forceinline__ void run(double (&u)[9], double uj, double nl) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %4, %5 row_newbcast:5 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %4, %5 row_newbcast:6 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %4, %5 row_newbcast:7 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %4, %5 row_newbcast:8 row_mask:0xf bank_mask:0xf\n"
-        : "+v"(u[5]), "+v"(u[6]), "+v"(u[7]), "+v"(u[8])
-        : "v"(uj), "v"(nl));
-  }
-};
-template <> struct PanelRest<4> {
-  static __device__ __forceinline__ void run(double (&u)[9], double uj, double nl) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %3, %4 row_newbcast:6 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %3, %4 row_newbcast:7 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %3, %4 row_newbcast:8 row_mask:0xf bank_mask:0xf\n"
-        : "+v"(u[6]), "+v"(u[7]), "+v"(u[8])
-        : "v"(uj), "v"(nl));
-  }
-};
-template <> struct PanelRest<5> {
-  static __device__ __forceinline__ void run(double (&u)[9], double uj, double nl) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %2, %3 row_newbcast:7 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %2, %3 row_newbcast:8 row_mask:0xf bank_mask:0xf\n"
-        : "+v"(u[7]), "+v"(u[8])
-        : "v"(uj), "v"(nl));
-  }
-};
-template <> struct PanelRest<6> {
-  static __device__ __forceinline__ void run(double (&u)[9], double uj, double nl) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %1, %2 row_newbcast:8 row_mask:0xf bank_mask:0xf\n"
-        : "+v"(u[8])
-        : "v"(uj), "v"(nl));
-  }
-};
-template <> struct PanelRest<7> {
-  static __device__ __forceinline__ void run(double (&u)[9], double uj, double nl) {
-    (void)u; (void)uj; (void)nl;
-  }
-};
-template <> struct PanelRest<8> {
-  static __device__ __forceinline__ void run(double (&u)[9], double uj, double nl) {
-    (void)u; (void)uj; (void)nl;
-  }
-};
-
-__global__ __launch_bounds__(kBlkWG) __attribute__((amdgpu_waves_per_eu(2))) void k_solve_blk(BaBatch bat) {
-  BA_PROB(bat);
-  lm_wave_priority();
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  double* red = lds;
-  int* fail_p = reinterpret_cast<int*>(lds + 16);
-  const int n = 9 * p.n_cams;
-  const BlkLds g(n);
-  double* Pn = lds + g.pn;
-  double* WL = lds + g.wl;
-  double* LL = lds + g.ll;
-  double* LF = lds + g.lf;
-  double* Dd = lds + g.dd;
-  double* Yy = lds + g.yy;
-  double* X = lds + g.xx;
-  const double* S = p.sys;
-  const double* bvec = S + (size_t)n * n;
-  const double* diagU = bvec + 2 * n;
-  const double lam = p.state[SLAM_BA_ST_LAMBDA];
-  const int t = threadIdx.x, lane = t & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int NT = g.n16 / 16, NL = NT * (NT + 1) / 2;
-  SOLVE_PROF_T(0);
-  SOLVE_TR(19, 1);
-  const int n2 = (n + 1) & ~1;
-  if (t == 0) *fail_p = 0;
-  for (int i = t; i < 2 * g.n16 * kWLs; i += kBlkWG) WL[i] = 0.0;  // WL and LL
-  // this wave's tiles: tl = wid + 4 s -> (I, J), I >= J.  All S loads are
-  // issued unconditionally (clamped addresses) before any is used.
-  int tI[kTileMax], tJ[kTileMax];
-  d4 acc[kTileMax];
-#pragma unroll
-  for (int s = 0; s < kTileMax; ++s) {
-    const int tl = wid + kBlkWaves * s;
-    int I = 0;
-    while ((I + 1) * (I + 2) / 2 <= tl) ++I;
-    tI[s] = tl < NL ? I : -1;
-    tJ[s] = tl < NL ? tl - I * (I + 1) / 2 : -1;
-    const int col = min(max(tJ[s], 0) * 16 + (lane & 15), n - 1);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int row = min(max(tI[s], 0) * 16 + (lane >> 4) + 4 * q, n - 1);
-      acc[s][q] = S[(size_t)row * n + col];
-    }
-  }
-  double* Eb = lds + g.ep;  // prefetch: b, g, diagU, live cameras, cost partials
-  {
-    const double* src[5] = {bvec, bvec + n, diagU, p.cams[cur_of(p.state)], diagU + n};
-    const int len[5] = {n, n, n, n, p.n_cams};
-    double v[5];  // n <= kLdsMaxN < kBlkWG: one element per thread, loads issued together
-#pragma unroll
-    for (int a = 0; a < 5; ++a) v[a] = src[a][min(t, len[a] - 1)];
-#pragma unroll
-    for (int a = 0; a < 5; ++a)
-      if (t < len[a]) Eb[a * n2 + t] = v[a];
-  }
-  __syncthreads();  // prefetched b and diagU
-#pragma unroll
-  for (int s = 0; s < kTileMax; ++s) {
-    const int col = tJ[s] * 16 + (lane & 15);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int row = tI[s] * 16 + (lane >> 4) + 4 * q;
-      double a = acc[s][q];
-      if (row == col) a += lam * clampd(Eb[2 * n2 + col]);
-      if (row == n) a = Eb[min(col, n - 1)];
-      if (tI[s] < 0 || col >= n || row > n) a = 0.0;
-      acc[s][q] = a;
-    }
-  }
-  SOLVE_PROF_T(1);
-  bool ok = true;
-  SOLVE_TR(19, 0);
-  for (int c0 = 0; c0 < n; c0 += kPanelW) {
-    SOLVE_TR(c0 / kPanelW, 0);
-    // (a) panel columns [c0, c0 + 9), rows c0..n -> Pn[row - c0][col - c0]
-#pragma unroll
-    for (int s = 0; s < kTileMax; ++s) {
-      if (tI[s] < 0 || tJ[s] * 16 + 15 < c0 || tJ[s] * 16 >= c0 + kPanelW || tI[s] * 16 + 15 < c0)
-        continue;  // uniform per wave
-      const int col = tJ[s] * 16 + (lane & 15);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int row = tI[s] * 16 + (lane >> 4) + 4 * q;
-        if (col >= c0 && col < c0 + kPanelW && col <= row && row >= c0 && row <= n)
-          Pn[(row - c0) * kPanelW + (col - c0)] = acc[s][q];
-      }
-    }
-    __syncthreads();
-    SOLVE_TR(c0 / kPanelW, 1);
-    // (b) panel factorisation, one panel row per lane: lanes 0..8 of every
-    // participating wave hold the 9 pivot rows r = c0 + m (lower entries),
-    // lanes 9..63 of wave w the rows c0 + 9 + 55 w + (lane - 9) (the rhs row n
-    // included).  Right-looking: at step j the pivot d_j and the column-j
-    // entries of the pivot rows are broadcast with v_readlane, and every lane
-    // eliminates its own row (u_i -= (u_j / d_j) A(c0+i, c0+j)).  Afterwards
-    // u_j is the partially eliminated entry A^{(j)}(r, c0+j), L(r, j) = u_j/d_j.
-    // (Was: every lane factored the whole 9x9 block redundantly, ~3x the
-    // VALU work of this form.)
-    // Every 16-lane DPP row of a participating wave holds a copy of the 9 pivot
-    // rows (lanes 0..8 of the row) and 7 rows below the panel (lanes 9..15), so
-    // the pivot entries reach the other lanes as DPP row_newbcast operands
-    // (no v_readlane -> SGPR hop in the pivot chain).  28 rows below per wave:
-    // 4 waves cover 9C + 1 - 9 <= 112 rows.
-    constexpr int kRowsBelow = 16 - kPanelW;              // per DPP row
-    const int nbelow = n + 1 - c0 - kPanelW;             // rows below the panel, rhs included
-    const int nw = max(1, (nbelow + 4 * kRowsBelow - 1) / (4 * kRowsBelow));  // uniform
-    if (wid < nw) {
-      const int rl = lane & 15, rg = lane >> 4;
-      const bool piv = rl < kPanelW;
-      const int r = piv ? c0 + rl
-                        : c0 + kPanelW + 4 * kRowsBelow * wid + kRowsBelow * rg + (rl - kPanelW);
-      const bool valid = r <= n;
-      const double* pr = Pn + (r - c0) * kPanelW;
-      double u[kPanelW];
-#pragma unroll
-      for (int j = 0; j < kPanelW; ++j) u[j] = valid && (!piv || j <= rl) ? pr[j] : 0.0;
-      double Dinv[kPanelW];
-      bool bad = false;
-      static_for<0, kPanelW>([&](auto J) {
-        constexpr int j = decltype(J)::value;
-        const double d = bcast16<j>(u[j]);
-        bad |= !(d > 0.0) || !isfinite(d);
-        Dinv[j] = rcp_f64(d);
-        const double l = u[j] * Dinv[j];
-        if constexpr (j + 1 < kPanelW) u[j + 1] = __builtin_fma(-l, bcast16<j + 1>(u[j]), u[j + 1]);
-        PanelRest<j>::run(u, u[j], -l);
-      });
-      // stores grouped so that each lane class takes one exec-mask region
-      if (valid && ((wid == 0 && rg == 0) || !piv)) {
-        double* wl = WL + r * kWLs;
-        double* ll = LL + r * kWLs;
-        double* lf = LF + r * (r - 1) / 2 + c0;
-        double lj[kPanelW];
-#pragma unroll
-        for (int j = 0; j < kPanelW; ++j) {
-          lj[j] = u[j] * Dinv[j];
-          wl[j] = -u[j];
-          ll[j] = lj[j];
-        }
-        if (r == n) {
-#pragma unroll
-          for (int j = 0; j < kPanelW; ++j) Yy[c0 + j] = u[j];
-        } else if (!piv) {
-#pragma unroll
-          for (int j = 0; j < kPanelW; ++j) lf[j] = lj[j];
-        } else {
-          // pivot row m = lane: D_m and the lower part L(r, c0 + j), j < m
-          double dm = u[0];
-#pragma unroll
-          for (int j = 1; j < kPanelW; ++j) dm = j == rl ? u[j] : dm;
-          Dd[r] = dm;
-#pragma unroll
-          for (int j = 0; j < kPanelW - 1; ++j)
-            if (j < rl) lf[j] = lj[j];
-        }
-      }
-      if (wid == 0 && lane == 0 && bad) *fail_p = 1;
-    }
-    SOLVE_TR(c0 / kPanelW, 2);
-    __syncthreads();
-    SOLVE_TR(c0 / kPanelW, 3);
-    if (*fail_p) {
-      ok = false;
-      break;
-    }
-    // (c) trailing update of the tiles right of / below the panel, tile by
-    // tile (6 operand loads, then its 3 MFMAs; each tile's sum in the same kk
-    // order).  Loading every live tile's operands first held ~100 more
-    // registers (317 per lane: one wave per SIMD, so a solve workgroup waited
-    // for a whole idle CU beside ORB); at 210 (two waves per SIMD) the batched
-    // local-BA stage in the tracking bench drops 3.1 -> 2.75 ms per step
-    // (profiles/r4/solve_lowreg_ab/ at git f26058c)
-    const int tr = c0 + kPanelW;
-#pragma unroll
-    for (int s = 0; s < kTileMax; ++s) {
-      if (!(tI[s] >= 0 && tJ[s] * 16 + 15 >= tr)) continue;  // uniform (I >= J)
-      const double* wrow = WL + (tI[s] * 16 + (lane & 15)) * kWLs + (lane >> 4);
-      const double* lrow = LL + (tJ[s] * 16 + (lane & 15)) * kWLs + (lane >> 4);
-      double wa[3], lb[3];
-#pragma unroll
-      for (int kk = 0; kk < 3; ++kk) {
-        wa[kk] = wrow[4 * kk];
-        lb[kk] = lrow[4 * kk];
-      }
-#pragma unroll
-      for (int kk = 0; kk < 3; ++kk)
-        acc[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(wa[kk], lb[kk], acc[s], 0, 0, 0);
-    }
-#ifdef SLAM_SOLVE_TRACE
-    if (threadIdx.x == 0) {
-      double chk = acc[0][0];
-      __asm__ volatile("" : "+v"(chk));
-      acc[0][0] = chk;
-    }
-    SOLVE_TR(c0 / kPanelW, 4);
-#endif
-  }
-  SOLVE_PROF_T(2);
-  SOLVE_TR(18, 0);
-  if (ok && wid == 0) {
-    // z = D^-1 y, then L^T x = z from the bottom; lane l holds rows l, l + 64.
-    // Step k: x_i -= L(k, i) x_k for i < k, x_k broadcast by v_readlane.  Rows
-    // k >= 64 update every x0 (i = lane < 64 <= k, no mask) and the x1 rows
-    // below k; rows k < 64 update x0 only.  The L rows of kBackU steps are
-    // loaded (clamped, then masked by a select) ahead of the dependent chain.
-    double x0 = lane < n ? Yy[lane] / Dd[lane] : 0.0;
-    double x1 = lane + 64 < n ? Yy[lane + 64] / Dd[lane + 64] : 0.0;
-    constexpr int kBackU = 8;
-    int k = n - 1;
-    for (; k - kBackU + 1 >= 64; k -= kBackU) {
-      double l0[kBackU], l1[kBackU];
-#pragma unroll
-      for (int u = 0; u < kBackU; ++u) {
-        const int kk = k - u;
-        const double* Lk = LF + kk * (kk - 1) / 2;
-        l0[u] = Lk[lane];
-        const double v = Lk[min(lane + 64, kk - 1)];
-        l1[u] = lane + 64 < kk ? v : 0.0;
-      }
-#pragma unroll
-      for (int u = 0; u < kBackU; ++u) {
-        const double xk = readlane_d(x1, k - u - 64);
-        x0 = __builtin_fma(-l0[u], xk, x0);
-        x1 = __builtin_fma(-l1[u], xk, x1);
-      }
-    }
-    for (; k >= 64; --k) {
-      const double* Lk = LF + k * (k - 1) / 2;
-      const double v = Lk[min(lane + 64, k - 1)];
-      const double xk = readlane_d(x1, k - 64);
-      x0 = __builtin_fma(-Lk[lane], xk, x0);
-      x1 = __builtin_fma(-(lane + 64 < k ? v : 0.0), xk, x1);
-    }
-    for (; k - kBackU + 1 >= 1; k -= kBackU) {
-      double l0[kBackU];
-#pragma unroll
-      for (int u = 0; u < kBackU; ++u) {
-        const int kk = k - u;
-        const double v = LF[kk * (kk - 1) / 2 + min(lane, kk - 1)];
-        l0[u] = lane < kk ? v : 0.0;
-      }
-#pragma unroll
-      for (int u = 0; u < kBackU; ++u) x0 = __builtin_fma(-l0[u], readlane_d(x0, k - u), x0);
-    }
-    for (; k >= 1; --k) {
-      const double v = LF[k * (k - 1) / 2 + min(lane, k - 1)];
-      x0 = __builtin_fma(-(lane < k ? v : 0.0), readlane_d(x0, k), x0);
-    }
-    if (lane < n) X[lane] = x0;
-    if (lane + 64 < n) X[lane + 64] = x1;
-  }
-  __syncthreads();
-  SOLVE_PROF_T(3);
-  SOLVE_TR(18, 1);
-  solve_epilogue(p, X, ok, red, EpiSrc{Eb + n2, Eb + 2 * n2, Eb + 3 * n2, Eb + 4 * n2});
-  SOLVE_PROF_END();
-  SOLVE_TR(18, 2);
-}
-
 // ---------------------------------------------------------------- tiled solve
 // Large reduced camera systems (9C > kLdsMaxN: the sharded C4 window, global
 // BA): blocked Cholesky LL^T over 64x64 f64 tiles in the nested-dissection
@@ -2348,238 +1721,6 @@ __device__ __forceinline__ void wave_lds_fence() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// Fused broadcast-FMA updates of the 16x16 register factor (v_fmac_f64 with a
-// DPP row_newbcast source: one instruction per update instead of a
-// v_mov_b64_dpp + v_fma_f64 pair -- the compiler does not combine 64-bit DPP
-// moves into VOP2).  FacRest<J>: v[m] += bcast_m(nl) * l for m = J+1..15;
-// InvRest<K>: s[i] += bcast_i(vk) * xk for i = K+1..15.  The leading s_nop 1
-// covers the VALU-write -> DPP-read hazard of the broadcast source; no
-// register these blocks write is read by a DPP (compiler or asm) before
-// compiler code rewrites it.  Bit for bit the products and sums of the
-// two-instruction form.
-template <int J> struct FacRest;
-template <int K> struct InvRest;
-template <> struct FacRest<0> {
-  static __device__ __forceinline__ void run(double (&v)[16], double nl, double l) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %15, %16 row_newbcast:1 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %15, %16 row_newbcast:2 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %15, %16 row_newbcast:3 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %15, %16 row_newbcast:4 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %4, %15, %16 row_newbcast:5 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %5, %15, %16 row_newbcast:6 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %6, %15, %16 row_newbcast:7 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %7, %15, %16 row_newbcast:8 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %8, %15, %16 row_newbcast:9 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %9, %15, %16 row_newbcast:10 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %10, %15, %16 row_newbcast:11 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %11, %15, %16 row_newbcast:12 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %12, %15, %16 row_newbcast:13 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %13, %15, %16 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %14, %15, %16 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(v[8]), "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15])
-                 : "v"(nl), "v"(l));
-  }
-};
-template <> struct FacRest<1> {
-  static __device__ __forceinline__ void run(double (&v)[16], double nl, double l) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %14, %15 row_newbcast:2 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %14, %15 row_newbcast:3 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %14, %15 row_newbcast:4 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %14, %15 row_newbcast:5 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %4, %14, %15 row_newbcast:6 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %5, %14, %15 row_newbcast:7 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %6, %14, %15 row_newbcast:8 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %7, %14, %15 row_newbcast:9 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %8, %14, %15 row_newbcast:10 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %9, %14, %15 row_newbcast:11 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %10, %14, %15 row_newbcast:12 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %11, %14, %15 row_newbcast:13 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %12, %14, %15 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %13, %14, %15 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(v[8]), "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15])
-                 : "v"(nl), "v"(l));
-  }
-};
-template <> struct FacRest<2> {
-  static __device__ __forceinline__ void run(double (&v)[16], double nl, double l) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %13, %14 row_newbcast:3 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %13, %14 row_newbcast:4 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %13, %14 row_newbcast:5 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %13, %14 row_newbcast:6 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %4, %13, %14 row_newbcast:7 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %5, %13, %14 row_newbcast:8 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %6, %13, %14 row_newbcast:9 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %7, %13, %14 row_newbcast:10 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %8, %13, %14 row_newbcast:11 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %9, %13, %14 row_newbcast:12 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %10, %13, %14 row_newbcast:13 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %11, %13, %14 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %12, %13, %14 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(v[8]), "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15])
-                 : "v"(nl), "v"(l));
-  }
-};
-template <> struct FacRest<3> {
-  static __device__ __forceinline__ void run(double (&v)[16], double nl, double l) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %12, %13 row_newbcast:4 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %12, %13 row_newbcast:5 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %12, %13 row_newbcast:6 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %12, %13 row_newbcast:7 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %4, %12, %13 row_newbcast:8 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %5, %12, %13 row_newbcast:9 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %6, %12, %13 row_newbcast:10 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %7, %12, %13 row_newbcast:11 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %8, %12, %13 row_newbcast:12 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %9, %12, %13 row_newbcast:13 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %10, %12, %13 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %11, %12, %13 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(v[8]), "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15])
-                 : "v"(nl), "v"(l));
-  }
-};
-template <> struct FacRest<4> {
-  static __device__ __forceinline__ void run(double (&v)[16], double nl, double l) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %11, %12 row_newbcast:5 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %11, %12 row_newbcast:6 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %11, %12 row_newbcast:7 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %11, %12 row_newbcast:8 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %4, %11, %12 row_newbcast:9 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %5, %11, %12 row_newbcast:10 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %6, %11, %12 row_newbcast:11 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %7, %11, %12 row_newbcast:12 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %8, %11, %12 row_newbcast:13 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %9, %11, %12 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %10, %11, %12 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(v[8]), "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15])
-                 : "v"(nl), "v"(l));
-  }
-};
-template <> struct FacRest<5> {
-  static __device__ __forceinline__ void run(double (&v)[16], double nl, double l) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %10, %11 row_newbcast:6 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %10, %11 row_newbcast:7 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %10, %11 row_newbcast:8 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %10, %11 row_newbcast:9 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %4, %10, %11 row_newbcast:10 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %5, %10, %11 row_newbcast:11 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %6, %10, %11 row_newbcast:12 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %7, %10, %11 row_newbcast:13 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %8, %10, %11 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %9, %10, %11 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(v[6]), "+v"(v[7]), "+v"(v[8]), "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15])
-                 : "v"(nl), "v"(l));
-  }
-};
-template <> struct FacRest<6> {
-  static __device__ __forceinline__ void run(double (&v)[16], double nl, double l) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %9, %10 row_newbcast:7 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %9, %10 row_newbcast:8 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %9, %10 row_newbcast:9 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %9, %10 row_newbcast:10 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %4, %9, %10 row_newbcast:11 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %5, %9, %10 row_newbcast:12 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %6, %9, %10 row_newbcast:13 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %7, %9, %10 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %8, %9, %10 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(v[7]), "+v"(v[8]), "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15])
-                 : "v"(nl), "v"(l));
-  }
-};
-template <> struct FacRest<7> {
-  static __device__ __forceinline__ void run(double (&v)[16], double nl, double l) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %8, %9 row_newbcast:8 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %8, %9 row_newbcast:9 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %8, %9 row_newbcast:10 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %8, %9 row_newbcast:11 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %4, %8, %9 row_newbcast:12 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %5, %8, %9 row_newbcast:13 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %6, %8, %9 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %7, %8, %9 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(v[8]), "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15])
-                 : "v"(nl), "v"(l));
-  }
-};
-template <> struct FacRest<8> {
-  static __device__ __forceinline__ void run(double (&v)[16], double nl, double l) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %7, %8 row_newbcast:9 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %7, %8 row_newbcast:10 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %7, %8 row_newbcast:11 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %7, %8 row_newbcast:12 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %4, %7, %8 row_newbcast:13 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %5, %7, %8 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %6, %7, %8 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15])
-                 : "v"(nl), "v"(l));
-  }
-};
-template <> struct FacRest<9> {
-  static __device__ __forceinline__ void run(double (&v)[16], double nl, double l) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %6, %7 row_newbcast:10 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %6, %7 row_newbcast:11 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %6, %7 row_newbcast:12 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %6, %7 row_newbcast:13 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %4, %6, %7 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %5, %6, %7 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15])
-                 : "v"(nl), "v"(l));
-  }
-};
-template <> struct FacRest<10> {
-  static __device__ __forceinline__ void run(double (&v)[16], double nl, double l) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %5, %6 row_newbcast:11 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %5, %6 row_newbcast:12 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %5, %6 row_newbcast:13 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %5, %6 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %4, %5, %6 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15])
-                 : "v"(nl), "v"(l));
-  }
-};
-template <> struct FacRest<11> {
-  static __device__ __forceinline__ void run(double (&v)[16], double nl, double l) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %4, %5 row_newbcast:12 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %4, %5 row_newbcast:13 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %4, %5 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %4, %5 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15])
-                 : "v"(nl), "v"(l));
-  }
-};
-template <> struct FacRest<12> {
-  static __device__ __forceinline__ void run(double (&v)[16], double nl, double l) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %3, %4 row_newbcast:13 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %3, %4 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %3, %4 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(v[13]), "+v"(v[14]), "+v"(v[15])
-                 : "v"(nl), "v"(l));
-  }
-};
-template <> struct FacRest<13> {
-  static __device__ __forceinline__ void run(double (&v)[16], double nl, double l) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %2, %3 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %2, %3 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(v[14]), "+v"(v[15])
-                 : "v"(nl), "v"(l));
-  }
-};
-template <> struct FacRest<14> {
-  static __device__ __forceinline__ void run(double (&v)[16], double nl, double l) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %1, %2 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(v[15])
-                 : "v"(nl), "v"(l));
-  }
-};
-template <> struct FacRest<15> {
-  static __device__ __forceinline__ void run(double (&v)[16], double nl, double l) {
-    (void)v; (void)nl; (void)l;
-  }
-};
-template <> struct InvRest<0> {
-  static __device__ __forceinline__ void run(double (&s)[16], double vk, double xk) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %15, %16 row_newbcast:1 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %15, %16 row_newbcast:2 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %15, %16 row_newbcast:3 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %15, %16 row_newbcast:4 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %4, %15, %16 row_newbcast:5 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %5, %15, %16 row_newbcast:6 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %6, %15, %16 row_newbcast:7 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %7, %15, %16 row_newbcast:8 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %8, %15, %16 row_newbcast:9 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %9, %15, %16 row_newbcast:10 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %10, %15, %16 row_newbcast:11 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %11, %15, %16 row_newbcast:12 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %12, %15, %16 row_newbcast:13 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %13, %15, %16 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %14, %15, %16 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(s[1]), "+v"(s[2]), "+v"(s[3]), "+v"(s[4]), "+v"(s[5]), "+v"(s[6]), "+v"(s[7]), "+v"(s[8]), "+v"(s[9]), "+v"(s[10]), "+v"(s[11]), "+v"(s[12]), "+v"(s[13]), "+v"(s[14]), "+v"(s[15])
-                 : "v"(vk), "v"(xk));
-  }
-};
-template <> struct InvRest<1> {
-  static __device__ __forceinline__ void run(double (&s)[16], double vk, double xk) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %14, %15 row_newbcast:2 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %14, %15 row_newbcast:3 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %14, %15 row_newbcast:4 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %14, %15 row_newbcast:5 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %4, %14, %15 row_newbcast:6 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %5, %14, %15 row_newbcast:7 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %6, %14, %15 row_newbcast:8 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %7, %14, %15 row_newbcast:9 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %8, %14, %15 row_newbcast:10 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %9, %14, %15 row_newbcast:11 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %10, %14, %15 row_newbcast:12 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %11, %14, %15 row_newbcast:13 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %12, %14, %15 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %13, %14, %15 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(s[2]), "+v"(s[3]), "+v"(s[4]), "+v"(s[5]), "+v"(s[6]), "+v"(s[7]), "+v"(s[8]), "+v"(s[9]), "+v"(s[10]), "+v"(s[11]), "+v"(s[12]), "+v"(s[13]), "+v"(s[14]), "+v"(s[15])
-                 : "v"(vk), "v"(xk));
-  }
-};
-template <> struct InvRest<2> {
-  static __device__ __forceinline__ void run(double (&s)[16], double vk, double xk) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %13, %14 row_newbcast:3 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %13, %14 row_newbcast:4 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %13, %14 row_newbcast:5 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %13, %14 row_newbcast:6 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %4, %13, %14 row_newbcast:7 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %5, %13, %14 row_newbcast:8 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %6, %13, %14 row_newbcast:9 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %7, %13, %14 row_newbcast:10 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %8, %13, %14 row_newbcast:11 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %9, %13, %14 row_newbcast:12 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %10, %13, %14 row_newbcast:13 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %11, %13, %14 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %12, %13, %14 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(s[3]), "+v"(s[4]), "+v"(s[5]), "+v"(s[6]), "+v"(s[7]), "+v"(s[8]), "+v"(s[9]), "+v"(s[10]), "+v"(s[11]), "+v"(s[12]), "+v"(s[13]), "+v"(s[14]), "+v"(s[15])
-                 : "v"(vk), "v"(xk));
-  }
-};
-template <> struct InvRest<3> {
-  static __device__ __forceinline__ void run(double (&s)[16], double vk, double xk) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %12, %13 row_newbcast:4 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %12, %13 row_newbcast:5 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %12, %13 row_newbcast:6 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %12, %13 row_newbcast:7 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %4, %12, %13 row_newbcast:8 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %5, %12, %13 row_newbcast:9 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %6, %12, %13 row_newbcast:10 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %7, %12, %13 row_newbcast:11 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %8, %12, %13 row_newbcast:12 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %9, %12, %13 row_newbcast:13 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %10, %12, %13 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %11, %12, %13 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(s[4]), "+v"(s[5]), "+v"(s[6]), "+v"(s[7]), "+v"(s[8]), "+v"(s[9]), "+v"(s[10]), "+v"(s[11]), "+v"(s[12]), "+v"(s[13]), "+v"(s[14]), "+v"(s[15])
-                 : "v"(vk), "v"(xk));
-  }
-};
-template <> struct InvRest<4> {
-  static __device__ __forceinline__ void run(double (&s)[16], double vk, double xk) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %11, %12 row_newbcast:5 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %11, %12 row_newbcast:6 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %11, %12 row_newbcast:7 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %11, %12 row_newbcast:8 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %4, %11, %12 row_newbcast:9 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %5, %11, %12 row_newbcast:10 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %6, %11, %12 row_newbcast:11 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %7, %11, %12 row_newbcast:12 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %8, %11, %12 row_newbcast:13 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %9, %11, %12 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %10, %11, %12 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(s[5]), "+v"(s[6]), "+v"(s[7]), "+v"(s[8]), "+v"(s[9]), "+v"(s[10]), "+v"(s[11]), "+v"(s[12]), "+v"(s[13]), "+v"(s[14]), "+v"(s[15])
-                 : "v"(vk), "v"(xk));
-  }
-};
-template <> struct InvRest<5> {
-  static __device__ __forceinline__ void run(double (&s)[16], double vk, double xk) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %10, %11 row_newbcast:6 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %10, %11 row_newbcast:7 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %10, %11 row_newbcast:8 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %10, %11 row_newbcast:9 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %4, %10, %11 row_newbcast:10 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %5, %10, %11 row_newbcast:11 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %6, %10, %11 row_newbcast:12 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %7, %10, %11 row_newbcast:13 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %8, %10, %11 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %9, %10, %11 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(s[6]), "+v"(s[7]), "+v"(s[8]), "+v"(s[9]), "+v"(s[10]), "+v"(s[11]), "+v"(s[12]), "+v"(s[13]), "+v"(s[14]), "+v"(s[15])
-                 : "v"(vk), "v"(xk));
-  }
-};
-template <> struct InvRest<6> {
-  static __device__ __forceinline__ void run(double (&s)[16], double vk, double xk) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %9, %10 row_newbcast:7 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %9, %10 row_newbcast:8 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %9, %10 row_newbcast:9 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %9, %10 row_newbcast:10 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %4, %9, %10 row_newbcast:11 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %5, %9, %10 row_newbcast:12 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %6, %9, %10 row_newbcast:13 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %7, %9, %10 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %8, %9, %10 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(s[7]), "+v"(s[8]), "+v"(s[9]), "+v"(s[10]), "+v"(s[11]), "+v"(s[12]), "+v"(s[13]), "+v"(s[14]), "+v"(s[15])
-                 : "v"(vk), "v"(xk));
-  }
-};
-template <> struct InvRest<7> {
-  static __device__ __forceinline__ void run(double (&s)[16], double vk, double xk) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %8, %9 row_newbcast:8 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %8, %9 row_newbcast:9 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %8, %9 row_newbcast:10 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %8, %9 row_newbcast:11 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %4, %8, %9 row_newbcast:12 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %5, %8, %9 row_newbcast:13 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %6, %8, %9 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %7, %8, %9 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(s[8]), "+v"(s[9]), "+v"(s[10]), "+v"(s[11]), "+v"(s[12]), "+v"(s[13]), "+v"(s[14]), "+v"(s[15])
-                 : "v"(vk), "v"(xk));
-  }
-};
-template <> struct InvRest<8> {
-  static __device__ __forceinline__ void run(double (&s)[16], double vk, double xk) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %7, %8 row_newbcast:9 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %7, %8 row_newbcast:10 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %7, %8 row_newbcast:11 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %7, %8 row_newbcast:12 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %4, %7, %8 row_newbcast:13 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %5, %7, %8 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %6, %7, %8 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(s[9]), "+v"(s[10]), "+v"(s[11]), "+v"(s[12]), "+v"(s[13]), "+v"(s[14]), "+v"(s[15])
-                 : "v"(vk), "v"(xk));
-  }
-};
-template <> struct InvRest<9> {
-  static __device__ __forceinline__ void run(double (&s)[16], double vk, double xk) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %6, %7 row_newbcast:10 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %6, %7 row_newbcast:11 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %6, %7 row_newbcast:12 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %6, %7 row_newbcast:13 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %4, %6, %7 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %5, %6, %7 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(s[10]), "+v"(s[11]), "+v"(s[12]), "+v"(s[13]), "+v"(s[14]), "+v"(s[15])
-                 : "v"(vk), "v"(xk));
-  }
-};
-template <> struct InvRest<10> {
-  static __device__ __forceinline__ void run(double (&s)[16], double vk, double xk) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %5, %6 row_newbcast:11 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %5, %6 row_newbcast:12 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %5, %6 row_newbcast:13 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %5, %6 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %4, %5, %6 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(s[11]), "+v"(s[12]), "+v"(s[13]), "+v"(s[14]), "+v"(s[15])
-                 : "v"(vk), "v"(xk));
-  }
-};
-template <> struct InvRest<11> {
-  static __device__ __forceinline__ void run(double (&s)[16], double vk, double xk) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %4, %5 row_newbcast:12 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %4, %5 row_newbcast:13 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %4, %5 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %3, %4, %5 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(s[12]), "+v"(s[13]), "+v"(s[14]), "+v"(s[15])
-                 : "v"(vk), "v"(xk));
-  }
-};
-template <> struct InvRest<12> {
-  static __device__ __forceinline__ void run(double (&s)[16], double vk, double xk) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %3, %4 row_newbcast:13 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %3, %4 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %2, %3, %4 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(s[13]), "+v"(s[14]), "+v"(s[15])
-                 : "v"(vk), "v"(xk));
-  }
-};
-template <> struct InvRest<13> {
-  static __device__ __forceinline__ void run(double (&s)[16], double vk, double xk) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %2, %3 row_newbcast:14 row_mask:0xf bank_mask:0xf\n" "v_fmac_f64_dpp %1, %2, %3 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(s[14]), "+v"(s[15])
-                 : "v"(vk), "v"(xk));
-  }
-};
-template <> struct InvRest<14> {
-  static __device__ __forceinline__ void run(double (&s)[16], double vk, double xk) {
-    asm("s_nop 1\n" "v_fmac_f64_dpp %0, %1, %2 row_newbcast:15 row_mask:0xf bank_mask:0xf\n"
-                 : "+v"(s[15])
-                 : "v"(vk), "v"(xk));
-  }
-};
-template <> struct InvRest<15> {
-  static __device__ __forceinline__ void run(double (&s)[16], double vk, double xk) {
-    (void)s; (void)vk; (void)xk;
-  }
-};
-
 // Wave 0's part of block column p: the 16x16 diagonal block of M factored in
 // registers and inverted (X_pp = L_pp^-1 into Xb); `ok` cleared on a
 // non-positive or non-finite pivot.
@@ -2608,7 +1749,7 @@ __device__ __forceinline__ void blk_factor_w0(double* M, double* Xb, int p, bool
     if constexpr (j + 1 < 16) dn = bcast16<j + 1>(__builtin_fma(-pj, pj, v[j + 1]));
     const double lij = i > j ? pj : (i == j ? djj * r : 0.0);
     v[j] = lij;
-    FacRest<j>::run(v, -pj, lij);
+    BcastFmaTail<j + 1, 15>::run(v, -pj, lij);
   });
   FAC_T(2 + 3 * p);  // (profiling build: wave 0's pivots of block p done)
   // column c = lane of L_pp^-1: x_c = 1 / l_cc, x_i = -(sum_{k<i} l_ik x_k) / l_ii
@@ -2625,7 +1766,7 @@ __device__ __forceinline__ void blk_factor_w0(double* M, double* Xb, int p, bool
   static_for<0, 16>([&](auto K) {
     constexpr int k = decltype(K)::value;
     x[k] = -sacc[k] * rj[k];
-    InvRest<k>::run(sacc, v[k], x[k]);
+    BcastFmaTail<k + 1, 15>::run(sacc, v[k], x[k]);
   });
   if (l < 16) {
     double* X = Xb + blk_id(p, p) * 16 * kBS17;
@@ -4269,16 +3410,6 @@ extern "C" int slam_ba_jacobian(const double* d_cams, const double* d_pts,
 
 namespace {
 
-// Descriptor batch of problems [i0, i0 + n) (n <= kBaMaxBatch) and the launch
-// extents that cover the largest of them.
-struct Launch {
-  BaBatch b;
-  int n, max_grps, max_blocks, max_sgrps, mode;
-  size_t solve_lds;
-  bool dense;
-  bool robust;  // a problem of the batch has loss != 0: the ROBUST kernels (each branches per problem)
-};
-
 // LDS floor of the one-workgroup camera solve (slam_ba_set_solve_lds_floor): a
 // floor above what a co-resident ORB workgroup leaves keeps the latency-bound
 // pivot chain off CUs whose SIMDs are busy with ORB waves.
@@ -4304,7 +3435,7 @@ static int make_launch(const slam_ba_problem* probs, int n, Launch* L) {
     L->max_grps = max(L->max_grps, probs[i].n_grps);
     L->max_sgrps = max(L->max_sgrps, probs[i].n_sgrps);
     L->max_blocks = max(L->max_blocks, probs[i].asm_act != nullptr ? probs[i].n_asm_act : probs[i].n_blocks);
-    L->solve_lds = std::max(L->solve_lds, sizeof(double) * BlkLds(9 * probs[i].n_cams).total);
+    L->solve_lds = std::max(L->solve_lds, slam::solve_blk_lds(probs[i].n_cams));
     L->solve_lds = std::max(L->solve_lds, g_solve_lds_floor);
     L->dense = L->dense && !sys_packed(probs[i].n_cams);
     L->robust = L->robust || probs[i].loss != 0;
@@ -4342,8 +3473,7 @@ static int launch_build(const Launch& L, hipStream_t s) {
 
 static int launch_solve(const Launch& L, bool fuse_decide, hipStream_t s) {
   if (L.dense) {
-    k_solve_blk<<<dim3(1, L.n), kBlkWG, L.solve_lds, s>>>(L.b);
-    SLAM_LAUNCHED("k_solve_blk");
+    if (int rc = slam::launch_solve_blk(L, s)) return rc;
   } else {
     if (tl_flow_ok(L.b.p[0], s)) {
       if (int rc = tl_solve_flow(L.b.p[0], s)) return rc;
@@ -4802,14 +3932,6 @@ extern "C" int slam_ba_covariance(const slam_ba_problem* prob, const int32_t* d_
   SLAM_LAUNCHED("k_cov_pick");
   return SLAM_OK;
 }
-
-#ifdef SLAM_SOLVE_TRACE
-extern "C" int slam_solve_trace(unsigned long long* out) {
-  SLAM_HIP(hipDeviceSynchronize());
-  SLAM_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_solve_trace), 20 * 6 * sizeof(unsigned long long)));
-  return SLAM_OK;
-}
-#endif
 
 #ifdef SLAM_LINM_PROFILE
 extern "C" int slam_linm_stamps(unsigned long long* out, int n) {

@@ -14,6 +14,7 @@
 // (mapping.hip k_map_assoc), q = (u - u_off, v - v_off); its points the first
 // M[w] entries of its map.  Reference: main.py:120-127 (local map -> BA
 // arguments), XXXport_files.py:44-64 (camera parameters, pixel offsets).
+#include "ba_layout.hpp"
 #include "common.hpp"
 
 #include <algorithm>
@@ -22,8 +23,6 @@
 
 namespace {
 using i64 = long long;
-constexpr int kCamRec = 32;   // ba.hip kCamRec
-constexpr int kCPart = 112;   // ba.hip kCPart
 constexpr int kNState = SLAM_BA_ST_SLOTS;
 i64 al32(i64 n) { return (std::max<i64>(n, 1) + 31) / 32 * 32; }  // BAWindowSet._al
 }  // namespace

@@ -12,7 +12,7 @@ Pose chain (live code; slam355.posegraph, csrc/posegraph.hip):
   bundle_adjustment_sparsity(car_params)                        (:159)
   bundle_adjustment_with_sparsity_without_loop_closure(car_params, sparse_mat) (:173)
   bundle_adjustment_with_sparsity(car_params, sparse_mat)       (:179)
-BAL reprojection BA (csrc/ba.hip):
+BAL reprojection BA (csrc/ba*.hip):
   read_bal_data(file_name)                                   (:236)
   objective(params, n_cams, n_Qs, cam_idxs, Q_idxs, qs)      (:331)
   bundle_adjustment_sparsity(n_cams, n_Qs, cam_idxs, Q_idxs) (:380)

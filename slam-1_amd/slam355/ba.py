@@ -2,7 +2,7 @@
 
 The planner turns a reference-style BA problem (BundleAdjustment.py:331:
 params = [cams (C x 9), points (P x 3)], cam_idxs, Q_idxs, qs) into the index
-tables the HIP kernels in csrc/ba.hip consume, allocates the device buffers
+tables the HIP kernels in csrc/ba*.hip consume, allocates the device buffers
 (torch tensors as HBM containers) and runs LM iterations with all state on the
 device.  Multi-GPU: each rank builds a BAProblem over ALL cameras and the
 observations of its own points; `step_distributed` all-reduces the reduced
@@ -187,7 +187,7 @@ def block_index(c1, c2, n_cams):
 
 def packed(n_cams):
     """True when the reduced camera system goes to the tiled solver in the packed
-    block layout (9C > 120; csrc/ba.hip sys_packed)."""
+    block layout (9C > 120; csrc/ba_common.hpp sys_packed)."""
     return 9 * n_cams > LDS_MAX_N
 
 
