@@ -597,12 +597,48 @@ int slam_ba_iterate_batch(const slam_ba_problem* probs, int n_probs, int n_iter,
  * are as before afterwards, but prob->sys is overwritten: a
  * slam_ba_build_system made before must be repeated before
  * slam_ba_solve_step (slam_ba_iterate rebuilds anyway).  Single rank: the
- * system of a landmark shard is not summed over ranks here.  Landmark
- * covariances are not computed. */
+ * system of a landmark shard is not summed over ranks here.  The landmark
+ * blocks of the same inverse: slam_ba_covariance_points. */
 long long slam_ba_cov_workspace_len(int n_cams);
 int slam_ba_covariance(const slam_ba_problem* prob, const int32_t* d_pairs, int n_pairs,
                        double rank_tol, double* d_cov, double* d_ws, long long ws_len,
                        int32_t* d_status, void* stream);
+
+/* Camera, landmark and landmark-camera blocks of (J^T J)^-1 from one build
+ * and one factorisation.  With Sigma_cc = S0^-1 as above, per
+ * observation o of point p and camera c(o) the Jacobian blocks Jc_o (2x9), Jp_o
+ * (2x3), W_o = Jc_o^T Jp_o, and V_p = sum_o Jp_o^T Jp_o (no damping):
+ *   Sigma_pp[p]    = V_p^-1 + V_p^-1 (sum_{o,o'} W_o^T Sigma_{c(o)c(o')} W_o') V_p^-1   (3x3)
+ *   Sigma_pc[p, c] = -V_p^-1 sum_o W_o^T Sigma_{c(o), c}                                (3x9)
+ * for any camera c, observing p or not; the sums run over the observations of
+ * p, so a repeated (point, camera) pair counts every time.
+ *   d_pairs  [n_pairs][2]  -> d_cov    [n_pairs][9][9]   as slam_ba_covariance (n_pairs may be 0)
+ *   d_points [n_points]    -> d_cov_pp [n_points][3][3]  point indices in the problem's (device)
+ *                             order; d_points NULL with n_points == n_pts: every point in order
+ *   d_cross  [n_cross][2]  -> d_cov_pc [n_cross][3][9]   (point, camera)
+ * An entry may repeat; each gets its own output row, and a row's bits do not
+ * depend on the rest of the request.  Sigma_pp is exactly symmetric; columns
+ * of held camera parameters in Sigma_pc are +0.0.  An index out of range gives
+ * a NaN row (never a read outside a buffer; the host wrapper checks first).
+ * d_status[0]: S0 not positive definite, as slam_ba_covariance (then every
+ * output is NaN).  A point is undetermined when a pivot of the unpivoted 3x3
+ * Cholesky of V_p is not finite or <= rank_tol * V_kk (no observation, one
+ * observation, a degenerate ray bundle): its requested rows are NaN and
+ * d_status[1] counts them; d_status[0] is not raised by it.  (S0 itself still
+ * takes such a point with the zero inverse of the LM steps when det V = 0 and
+ * with a huge inverse otherwise: drop one-observation points from a problem
+ * whose camera blocks matter.)
+ * Refused before any launch: all three counts 0, a negative count, a non-zero
+ * count with a null list or output (except the all-points form), and what
+ * slam_ba_covariance refuses for rank_tol and the workspace (the same
+ * slam_ba_cov_workspace_len doubles).  Stream, allocation, LM state and
+ * prob->sys as slam_ba_covariance. */
+int slam_ba_covariance_points(const slam_ba_problem* prob,
+                              const int32_t* d_pairs, int n_pairs, double* d_cov,
+                              const int32_t* d_points, int n_points, double* d_cov_pp,
+                              const int32_t* d_cross, int n_cross, double* d_cov_pc,
+                              double rank_tol, double* d_ws, long long ws_len,
+                              int32_t* d_status /* [2] */, void* stream);
 
 /* Minimum dynamic LDS (bytes, <= 160 KiB) the one-workgroup camera solve
  * (9C <= 120) requests; 0 (default) = what it needs.  A floor above what

@@ -3876,6 +3876,284 @@ __global__ __launch_bounds__(128) void k_cov_pick(slam_ba_problem p, const int32
   cov[(size_t)q * 81 + t] = v;
 }
 
+// ---------------------------------------------------------------- landmark covariance
+// Point blocks Sigma_pp and point-camera blocks Sigma_pc of the same inverse
+// (DESIGN.md 4c), from Sigma_cc as k_cov_sigma left it: per observation o of a
+// point, J~ = (Jc | Jp) as k_linearize forms it, and
+//   Sigma_pp = V^-1 + V^-1 (sum_{o,o'} Jp_o^T (Jc_o Sigma_{c(o)c(o')} Jc_o'^T) Jp_o') V^-1,
+//   Sigma_pc = -V^-1 sum_o Jp_o^T (Jc_o Sigma_{c(o),c}),      V = sum_o Jp_o^T Jp_o
+// (W_o^T Sigma W_o' with W = Jc^T Jp, the 2 x 2 middle factor formed first:
+// 24 staged doubles per observation instead of 33, 230 multiplies per pair
+// instead of 324).  One wave per requested entry, kCovPW entries per
+// workgroup; the waves never meet (no __syncthreads), sums are fixed shuffle
+// trees, so an entry's bits do not depend on the request around it.
+constexpr int kCovPW = 4;   // waves per workgroup
+constexpr int kCovCh = 8;   // observations per chunk: a step covers the 8 x 8 ordered pairs of two chunks
+constexpr int kCovJS = 25;  // LDS stride of a staged 2 x 12 Jacobian (odd: rows spread over the banks)
+
+__device__ __forceinline__ double cov_sig(const double* __restrict__ ws, const CovLayout& L, int i, int j) {
+  return ws[L.a + (size_t)max(i, j) * L.N + min(i, j)];
+}
+
+// J~ of observation o: the steps of k_linearize in its order
+__device__ __forceinline__ void cov_obs_jac(const slam_ba_problem& p, int cur, int o, double J[2][12]) {
+  double r[2];
+  const int c = p.obs_cam[o];
+  reproject_pre<true>(p.camrec[cur] + kCamRec * c, p.pts[cur] + 3 * p.obs_pt[o], p.obs_q + 2 * o, r, J);
+  clamp_rows<true>(r, J);
+  if (p.cam_fixed != nullptr) hold_cols(J, p.cam_fixed[c]);
+  if (p.loss != 0) robust_weight<12>(r, J[0], J[1], p.loss, p.loss_scale);
+}
+
+// the tree of block_sum over one wave; the sum on every lane
+__device__ __forceinline__ double wave_sum(double v) {
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return __shfl(v, 0, 64);
+}
+
+__device__ __forceinline__ void cov_mark_block(int* need, int T, int a, int b) {
+  for (int ta = 9 * a / kTB; ta <= (9 * a + 8) / kTB; ++ta)
+    for (int tb = 9 * b / kTB; tb <= (9 * b + 8) / kTB; ++tb) need[max(ta, tb) * T + min(ta, tb)] = 1;
+}
+
+// The lower tiles the point and cross requests read: blocks (c(o), c(o')) of a
+// requested point, (c(o), c) of a requested (point, camera).  One lane per entry.
+__global__ __launch_bounds__(kBS) void k_cov_mark_pts(slam_ba_problem p, const int32_t* __restrict__ points,
+                                                      int n_points, const int32_t* __restrict__ cross,
+                                                      int n_cross, double* ws) {
+  const CovLayout L(p.n_cams);
+  const int q = blockIdx.x * kBS + threadIdx.x;
+  if (q >= n_points + n_cross) return;
+  int* need = reinterpret_cast<int*>(ws + L.need);
+  const bool is_pt = q < n_points;
+  const int pt = is_pt ? (points ? points[q] : q) : cross[2 * (q - n_points)];
+  const int c = is_pt ? 0 : cross[2 * (q - n_points) + 1];
+  if ((unsigned)pt >= (unsigned)p.n_pts || (unsigned)c >= (unsigned)p.n_cams) return;
+  const int o0 = p.pt_ptr[pt], o1 = p.pt_ptr[pt + 1];
+  for (int o = o0; o < o1; ++o) {
+    const int a = p.obs_cam[o];
+    if (!is_pt) {
+      cov_mark_block(need, L.T, a, c);
+      continue;
+    }
+    for (int o2 = o0; o2 <= o; ++o2) cov_mark_block(need, L.T, a, p.obs_cam[o2]);  // (a, b) and (b, a): one lower tile
+  }
+}
+
+// Both status words of slam_ba_covariance_points, before the kernels that count.
+__global__ void k_cov_status(slam_ba_problem p, const double* __restrict__ ws, int32_t* __restrict__ status) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  status[0] = cov_failed(ws, CovLayout(p.n_cams)) ? 1 : 0;
+  status[1] = 0;
+}
+
+// V^-1 of point pt by a whole wave, the same on every lane: lanes over the
+// observations, the six sums by wave_sum, the pivots of the unpivoted 3x3
+// Cholesky (as squares: d_k of L D L^T) against rank_tol V_kk, the inverse by
+// cofactors.  false: the point is undetermined.
+__device__ __forceinline__ bool cov_point_vinv(const slam_ba_problem& p, int cur, int pt, double rank_tol,
+                                               double iv[6]) {
+  const int lane = threadIdx.x & 63;
+  const int o0 = p.pt_ptr[pt], o1 = p.pt_ptr[pt + 1];
+  double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int ob = o0; ob < o1; ob += 64) {
+    const int o = ob + lane;
+    if (o < o1) {
+      double J[2][12];
+      cov_obs_jac(p, cur, o, J);
+#pragma unroll
+      for (int a = 0; a < 2; ++a) {
+        v[0] += J[a][9] * J[a][9];
+        v[1] += J[a][9] * J[a][10];
+        v[2] += J[a][9] * J[a][11];
+        v[3] += J[a][10] * J[a][10];
+        v[4] += J[a][10] * J[a][11];
+        v[5] += J[a][11] * J[a][11];
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) v[k] = wave_sum(v[k]);
+  const double a00 = v[0], a01 = v[1], a02 = v[2], a11 = v[3], a12 = v[4], a22 = v[5];
+  const double d0 = a00;
+  const double l10 = a01 / d0, l20 = a02 / d0;
+  const double d1 = a11 - l10 * a01;
+  const double u21 = a12 - l20 * a01;
+  const double d2 = a22 - l20 * a02 - (u21 / d1) * u21;
+  const double c00 = a11 * a22 - a12 * a12;
+  const double c01 = a02 * a12 - a01 * a22;
+  const double c02 = a01 * a12 - a02 * a11;
+  const double c11 = a00 * a22 - a02 * a02;
+  const double c12 = a01 * a02 - a00 * a12;
+  const double c22 = a00 * a11 - a01 * a01;
+  const double det = a00 * c00 + a01 * c01 + a02 * c02;
+  const bool ok = d0 > rank_tol * a00 && d0 < INFINITY && d1 > rank_tol * a11 && d1 < INFINITY &&
+                  d2 > rank_tol * a22 && d2 < INFINITY && det > 0.0 && det < INFINITY;  // (a NaN fails every test)
+  const double id = 1.0 / det;
+  iv[0] = c00 * id; iv[1] = c01 * id; iv[2] = c02 * id;
+  iv[3] = c11 * id; iv[4] = c12 * id; iv[5] = c22 * id;
+  return ok;
+}
+
+// Sigma_pp of the requested points, [n_points][3][3].  A wave walks the pairs of
+// 8-observation chunks (A, B) of its point: lanes 0..15 stage the J~ of the two
+// chunks in LDS (recomputed per step: nothing of the point is kept beyond 16
+// rows, so a deep point needs no more LDS than a shallow one), lane (a, b)
+// adds observation pair (8A + a, 8B + b) to its six entries.
+__global__ __launch_bounds__(64 * kCovPW) void k_cov_points(slam_ba_problem p, const int32_t* __restrict__ points,
+                                                            int n_points, double rank_tol,
+                                                            const double* __restrict__ ws,
+                                                            double* __restrict__ cov_pp,
+                                                            int32_t* __restrict__ status) {
+  __shared__ double Js[kCovPW][2 * kCovCh][kCovJS];
+  __shared__ int Cs[kCovPW][2 * kCovCh];
+  const CovLayout L(p.n_cams);
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int q = blockIdx.x * kCovPW + w;
+  if (q >= n_points) return;
+  const int pt = points ? points[q] : q;
+  double* out = cov_pp + (size_t)q * 9;
+  if (cov_failed(ws, L) || (unsigned)pt >= (unsigned)p.n_pts) {
+    if (lane < 9) out[lane] = __builtin_nan("");
+    return;
+  }
+  const int cur = cur_of(p.state);
+  double iv[6];
+  if (!cov_point_vinv(p, cur, pt, rank_tol, iv)) {
+    if (lane < 9) out[lane] = __builtin_nan("");
+    if (lane == 0) atomicAdd(status + 1, 1);
+    return;
+  }
+  const int o0 = p.pt_ptr[pt], n = p.pt_ptr[pt + 1] - o0;
+  const int nch = (n + kCovCh - 1) / kCovCh;
+  const int a = lane >> 3, b = lane & 7;
+  double m[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int A = 0; A < nch; ++A)
+    for (int B = 0; B < nch; ++B) {
+      if (lane < 2 * kCovCh) {
+        const int k = (lane < kCovCh ? A : B) * kCovCh + (lane & (kCovCh - 1));
+        if (k < n) {
+          double J[2][12];
+          cov_obs_jac(p, cur, o0 + k, J);
+#pragma unroll
+          for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int i = 0; i < 12; ++i) Js[w][lane][12 * r + i] = J[r][i];
+          Cs[w][lane] = p.obs_cam[o0 + k];
+        }
+      }
+      wave_lds_fence();
+      if (A * kCovCh + a < n && B * kCovCh + b < n) {
+        const double* Ja = Js[w][a];
+        const double* Jb = Js[w][kCovCh + b];
+        const int ia = 9 * Cs[w][a], ib = 9 * Cs[w][kCovCh + b];
+        double g00 = 0.0, g01 = 0.0, g10 = 0.0, g11 = 0.0;  // Jc_a Sigma_{c(a) c(b)} Jc_b^T
+        for (int s = 0; s < 9; ++s) {
+          double t0 = 0.0, t1 = 0.0;
+#pragma unroll
+          for (int r = 0; r < 9; ++r) {
+            const double sg = cov_sig(ws, L, ia + r, ib + s);
+            t0 += Ja[r] * sg;
+            t1 += Ja[12 + r] * sg;
+          }
+          g00 += t0 * Jb[s];
+          g01 += t0 * Jb[12 + s];
+          g10 += t1 * Jb[s];
+          g11 += t1 * Jb[12 + s];
+        }
+        int e = 0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          const double h0 = Ja[9 + i] * g00 + Ja[21 + i] * g10, h1 = Ja[9 + i] * g01 + Ja[21 + i] * g11;
+#pragma unroll
+          for (int j = i; j < 3; ++j) m[e++] += h0 * Jb[9 + j] + h1 * Jb[21 + j];
+        }
+      }
+      wave_lds_fence();  // the rows are staged again in the next step
+    }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) m[k] = wave_sum(m[k]);
+  if (lane != 0) return;
+  // V^-1 + V^-1 (M V^-1): six entries, mirrored
+  const double M[3][3] = {{m[0], m[1], m[2]}, {m[1], m[3], m[4]}, {m[2], m[4], m[5]}};
+  const double IV[3][3] = {{iv[0], iv[1], iv[2]}, {iv[1], iv[3], iv[4]}, {iv[2], iv[4], iv[5]}};
+  double X[3][3], S[3][3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) X[i][j] = M[i][0] * IV[0][j] + M[i][1] * IV[1][j] + M[i][2] * IV[2][j];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = i; j < 3; ++j)
+      S[i][j] = S[j][i] = IV[i][j] + (IV[i][0] * X[0][j] + IV[i][1] * X[1][j] + IV[i][2] * X[2][j]);
+#pragma unroll
+  for (int i = 0; i < 9; ++i) out[i] = S[i / 3][i % 3];
+}
+
+// Sigma_pc of the requested (point, camera) entries, [n_cross][3][9]: lanes over
+// the point's observations, 27 sums by wave_sum, then -V^-1 . ; +0.0 in the
+// columns of held parameters of the camera.
+__global__ __launch_bounds__(64 * kCovPW) void k_cov_cross(slam_ba_problem p, const int32_t* __restrict__ cross,
+                                                           int n_cross, double rank_tol,
+                                                           const double* __restrict__ ws,
+                                                           double* __restrict__ cov_pc,
+                                                           int32_t* __restrict__ status) {
+  const CovLayout L(p.n_cams);
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int q = blockIdx.x * kCovPW + w;
+  if (q >= n_cross) return;
+  const int pt = cross[2 * q], c = cross[2 * q + 1];
+  double* out = cov_pc + (size_t)q * 27;
+  if (cov_failed(ws, L) || (unsigned)pt >= (unsigned)p.n_pts || (unsigned)c >= (unsigned)p.n_cams) {
+    if (lane < 27) out[lane] = __builtin_nan("");
+    return;
+  }
+  const int cur = cur_of(p.state);
+  double iv[6];
+  if (!cov_point_vinv(p, cur, pt, rank_tol, iv)) {
+    if (lane < 27) out[lane] = __builtin_nan("");
+    if (lane == 0) atomicAdd(status + 1, 1);
+    return;
+  }
+  const int o0 = p.pt_ptr[pt], o1 = p.pt_ptr[pt + 1];
+  double acc[27];
+#pragma unroll
+  for (int k = 0; k < 27; ++k) acc[k] = 0.0;
+  for (int ob = o0; ob < o1; ob += 64) {
+    const int o = ob + lane;
+    if (o < o1) {
+      double J[2][12];
+      cov_obs_jac(p, cur, o, J);
+      const int ia = 9 * p.obs_cam[o];
+#pragma unroll
+      for (int s = 0; s < 9; ++s) {
+        double t0 = 0.0, t1 = 0.0;  // (Jc_o Sigma_{c(o), c})[:, s]
+#pragma unroll
+        for (int r = 0; r < 9; ++r) {
+          const double sg = cov_sig(ws, L, ia + r, 9 * c + s);
+          t0 += J[0][r] * sg;
+          t1 += J[1][r] * sg;
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) acc[9 * i + s] += J[0][9 + i] * t0 + J[1][9 + i] * t1;
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 27; ++k) acc[k] = wave_sum(acc[k]);
+  if (lane != 0) return;
+  const unsigned fx = p.cam_fixed != nullptr ? p.cam_fixed[c] : 0u;
+  const double IV[3][3] = {{iv[0], iv[1], iv[2]}, {iv[1], iv[3], iv[4]}, {iv[2], iv[4], iv[5]}};
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int s = 0; s < 9; ++s) {
+      const double v = 0.0 - (IV[i][0] * acc[s] + IV[i][1] * acc[9 + s] + IV[i][2] * acc[18 + s]);  // (never -0.0)
+      out[9 * i + s] = ((fx >> s) & 1u) ? 0.0 : v;
+    }
+}
+
 }  // namespace
 
 extern "C" long long slam_ba_cov_workspace_len(int n_cams) {
@@ -3883,22 +4161,21 @@ extern "C" long long slam_ba_cov_workspace_len(int n_cams) {
   return CovLayout(n_cams).total;
 }
 
-extern "C" int slam_ba_covariance(const slam_ba_problem* prob, const int32_t* d_pairs, int n_pairs,
-                                  double rank_tol, double* d_cov, double* d_ws, long long ws_len,
-                                  int32_t* d_status, void* stream) {
-  Launch La;
-  if (int rc = make_launch(prob, 1, &La)) return rc;
-  SLAM_REQUIRE(n_pairs >= 1, "slam_ba_covariance: n_pairs %d < 1", n_pairs);
-  SLAM_REQUIRE(std::isfinite(rank_tol) && rank_tol >= 0.0 && rank_tol < 1.0,
-               "slam_ba_covariance: rank_tol %g must be finite and in [0, 1)", rank_tol);
-  SLAM_REQUIRE(d_pairs && d_cov && d_status, "slam_ba_covariance: null pointer");
-  const CovLayout L(prob->n_cams);
-  SLAM_REQUIRE(d_ws != nullptr && ws_len >= L.total,
-               "slam_ba_covariance: workspace of %lld doubles, slam_ba_cov_workspace_len gives %lld",
-               d_ws ? ws_len : 0ll, L.total);
-  hipStream_t s = slam::as_stream(stream);
+namespace {
+
+struct CovRequest {
+  const int32_t* pairs;   int n_pairs;  double* cov;      // camera blocks (k_cov_mark, k_cov_pick)
+  const int32_t* points;  int n_points; double* cov_pp;   // point blocks (null list: every point in order)
+  const int32_t* cross;   int n_cross;  double* cov_pc;   // (point, camera) blocks
+  bool two_words;                                         // d_status [2] (slam_ba_covariance_points)
+};
+
+// The launches of both covariance entry points: one build at lambda = 0, one
+// factorisation, Sigma on the marked tiles, then the requested blocks.
+int cov_launch(const Launch& La, const CovRequest& rq, double rank_tol, double* d_ws, int32_t* d_status,
+               hipStream_t s) {
   const slam_ba_problem& p = La.b.p[0];
-  const int T = L.T;
+  const int T = CovLayout(p.n_cams).T;
   k_cov_lambda<<<1, 64, 0, s>>>(p, d_ws, 0);
   SLAM_LAUNCHED("k_cov_lambda");
   const int rc = launch_build(La, s);
@@ -3911,8 +4188,15 @@ extern "C" int slam_ba_covariance(const slam_ba_problem* prob, const int32_t* d_
     k_cov_scatter<<<p.n_blocks, 128, 0, s>>>(p, d_ws);
     SLAM_LAUNCHED("k_cov_scatter");
   }
-  k_cov_mark<<<nblk(n_pairs, kBS), kBS, 0, s>>>(p, d_pairs, n_pairs, d_ws);
-  SLAM_LAUNCHED("k_cov_mark");
+  if (rq.n_pairs > 0) {
+    k_cov_mark<<<nblk(rq.n_pairs, kBS), kBS, 0, s>>>(p, rq.pairs, rq.n_pairs, d_ws);
+    SLAM_LAUNCHED("k_cov_mark");
+  }
+  if (rq.n_points + rq.n_cross > 0) {
+    k_cov_mark_pts<<<nblk(rq.n_points + rq.n_cross, kBS), kBS, 0, s>>>(p, rq.points, rq.n_points, rq.cross,
+                                                                      rq.n_cross, d_ws);
+    SLAM_LAUNCHED("k_cov_mark_pts");
+  }
   for (int k = 0; k < T; ++k) {
     k_cov_panel<<<T - k, kTlWG, 0, s>>>(p, d_ws, k, rank_tol);
     SLAM_LAUNCHED("k_cov_panel");
@@ -3928,9 +4212,70 @@ extern "C" int slam_ba_covariance(const slam_ba_problem* prob, const int32_t* d_
   }
   k_cov_sigma<<<T * (T + 1) / 2, kTlWG, 0, s>>>(p, d_ws);
   SLAM_LAUNCHED("k_cov_sigma");
-  k_cov_pick<<<n_pairs, 128, 0, s>>>(p, d_pairs, d_ws, d_cov, d_status);
-  SLAM_LAUNCHED("k_cov_pick");
+  if (rq.two_words) {
+    k_cov_status<<<1, 64, 0, s>>>(p, d_ws, d_status);
+    SLAM_LAUNCHED("k_cov_status");
+  }
+  if (rq.n_pairs > 0) {
+    k_cov_pick<<<rq.n_pairs, 128, 0, s>>>(p, rq.pairs, d_ws, rq.cov, d_status);
+    SLAM_LAUNCHED("k_cov_pick");
+  }
+  if (rq.n_points > 0) {
+    k_cov_points<<<nblk(rq.n_points, kCovPW), 64 * kCovPW, 0, s>>>(p, rq.points, rq.n_points, rank_tol, d_ws,
+                                                                  rq.cov_pp, d_status);
+    SLAM_LAUNCHED("k_cov_points");
+  }
+  if (rq.n_cross > 0) {
+    k_cov_cross<<<nblk(rq.n_cross, kCovPW), 64 * kCovPW, 0, s>>>(p, rq.cross, rq.n_cross, rank_tol, d_ws,
+                                                                rq.cov_pc, d_status);
+    SLAM_LAUNCHED("k_cov_cross");
+  }
   return SLAM_OK;
+}
+
+}  // namespace
+
+extern "C" int slam_ba_covariance(const slam_ba_problem* prob, const int32_t* d_pairs, int n_pairs,
+                                  double rank_tol, double* d_cov, double* d_ws, long long ws_len,
+                                  int32_t* d_status, void* stream) {
+  Launch La;
+  if (int rc = make_launch(prob, 1, &La)) return rc;
+  SLAM_REQUIRE(n_pairs >= 1, "slam_ba_covariance: n_pairs %d < 1", n_pairs);
+  SLAM_REQUIRE(std::isfinite(rank_tol) && rank_tol >= 0.0 && rank_tol < 1.0,
+               "slam_ba_covariance: rank_tol %g must be finite and in [0, 1)", rank_tol);
+  SLAM_REQUIRE(d_pairs && d_cov && d_status, "slam_ba_covariance: null pointer");
+  const CovLayout L(prob->n_cams);
+  SLAM_REQUIRE(d_ws != nullptr && ws_len >= L.total,
+               "slam_ba_covariance: workspace of %lld doubles, slam_ba_cov_workspace_len gives %lld",
+               d_ws ? ws_len : 0ll, L.total);
+  const CovRequest rq{d_pairs, n_pairs, d_cov, nullptr, 0, nullptr, nullptr, 0, nullptr, false};
+  return cov_launch(La, rq, rank_tol, d_ws, d_status, slam::as_stream(stream));
+}
+
+extern "C" int slam_ba_covariance_points(const slam_ba_problem* prob, const int32_t* d_pairs, int n_pairs,
+                                         double* d_cov, const int32_t* d_points, int n_points,
+                                         double* d_cov_pp, const int32_t* d_cross, int n_cross,
+                                         double* d_cov_pc, double rank_tol, double* d_ws, long long ws_len,
+                                         int32_t* d_status, void* stream) {
+  Launch La;
+  if (int rc = make_launch(prob, 1, &La)) return rc;
+  SLAM_REQUIRE(n_pairs >= 0 && n_points >= 0 && n_cross >= 0,
+               "slam_ba_covariance_points: negative count (n_pairs %d, n_points %d, n_cross %d)", n_pairs,
+               n_points, n_cross);
+  SLAM_REQUIRE(n_pairs + (long long)n_points + n_cross >= 1, "slam_ba_covariance_points: nothing requested");
+  SLAM_REQUIRE(std::isfinite(rank_tol) && rank_tol >= 0.0 && rank_tol < 1.0,
+               "slam_ba_covariance_points: rank_tol %g must be finite and in [0, 1)", rank_tol);
+  SLAM_REQUIRE(d_status != nullptr && (n_pairs == 0 || (d_pairs && d_cov)) &&
+                   (n_points == 0 || (d_cov_pp && (d_points || n_points == prob->n_pts))) &&
+                   (n_cross == 0 || (d_cross && d_cov_pc)),
+               "slam_ba_covariance_points: null pointer (a null d_points needs n_points == n_pts = %d)",
+               prob->n_pts);
+  const CovLayout L(prob->n_cams);
+  SLAM_REQUIRE(d_ws != nullptr && ws_len >= L.total,
+               "slam_ba_covariance_points: workspace of %lld doubles, slam_ba_cov_workspace_len gives %lld",
+               d_ws ? ws_len : 0ll, L.total);
+  const CovRequest rq{d_pairs, n_pairs, d_cov, d_points, n_points, d_cov_pp, d_cross, n_cross, d_cov_pc, true};
+  return cov_launch(La, rq, rank_tol, d_ws, d_status, slam::as_stream(stream));
 }
 
 #ifdef SLAM_LINM_PROFILE

@@ -115,6 +115,8 @@ SIGNATURES = {
     "slam_ba_iterate_batch": [_PROB, c_int, c_int, c_p],
     "slam_ba_cov_workspace_len": [c_int],
     "slam_ba_covariance": [_PROB, c_p, c_int, c_double, c_p, c_p, c_longlong, c_p, c_p],
+    "slam_ba_covariance_points": [_PROB, c_p, c_int, c_p, c_p, c_int, c_p, c_p, c_int, c_p, c_double, c_p,
+                                  c_longlong, c_p, c_p],
     "slam_ba_set_solve_lds_floor": [c_int],
     "slam_orb_set_lds_floor": [c_int],
     "slam_count_min": [c_p, c_int, c_p, c_p],

@@ -23,9 +23,14 @@ Covariance: `BAProblem.covariance` / `BABatch.covariance` (cov_pairs) return
 marginal 9x9 covariance blocks of the camera parameters at the live
 parameters, from the reduced camera system at zero damping, inverted on the
 device.  The caller fixes the gauge with `fixed`.
+`BAProblem.point_covariance` / `BABatch.point_covariance` (cov_points,
+cov_cross) add the landmark blocks (3x3) and landmark-camera blocks (3x9) of
+the same inverse, `BAProblem.reprojection_covariance` the 2x2 covariance of a
+landmark's predicted pixel in a camera.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 
@@ -111,6 +116,27 @@ def loss_args(loss, f_scale=1.0):
 
 
 # ----------------------------------------------------------------------------- covariance
+def _cov_ints(a, what, bounds):
+    """`a` as a contiguous int32 index list: [m] in [0, bounds[0]) for one
+    bound, [m, k] with column j in [0, bounds[j]) for k bounds.  ValueError on
+    a non-integer dtype (an empty input of any dtype passes), another shape or
+    an index out of range."""
+    k = len(bounds)
+    a = np.asarray(a)
+    if a.size == 0:
+        a = np.zeros((0,) if k == 1 else (0, k), np.int64)
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"{what} must be integer indices")
+    if a.ndim != (1 if k == 1 else 2) or (k > 1 and a.shape[1] != k):
+        raise ValueError(f"{what} must have shape {'[m]' if k == 1 else f'[m, {k}]'}, not {list(a.shape)}")
+    a = a.astype(np.int64)
+    for j, n in enumerate(bounds):
+        col = a if k == 1 else a[:, j]
+        if col.size and (col.min() < 0 or col.max() >= n):
+            raise ValueError(f"{what}: index out of range [0, {n})")
+    return np.ascontiguousarray(a.astype(np.int32))
+
+
 def cov_pairs(n_cams, cameras=None, pairs=None):
     """The int32 [m, 2] block list of slam_ba_covariance: (a, a) for every
     camera a of `cameras` (their marginal blocks), then the (a, b) of `pairs`
@@ -120,37 +146,47 @@ def cov_pairs(n_cams, cameras=None, pairs=None):
     n_cams = int(n_cams)
     if n_cams < 1:
         raise ValueError("n_cams must be >= 1")
-
-    def ints(a, what):
-        a = np.asarray(a)
-        if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
-            if a.size:
-                raise ValueError(f"{what} must be integer camera indices")
-            a = a.astype(np.int64)
-        a = a.astype(np.int64)
-        if a.size and (a.min() < 0 or a.max() >= n_cams):
-            raise ValueError(f"{what}: camera index out of range [0, {n_cams})")
-        return a
-
     if cameras is None and pairs is None:
         cameras = np.arange(n_cams)
     out = []
     if cameras is not None:
-        c = ints(cameras, "cameras")
-        if c.ndim != 1:
-            raise ValueError("cameras must be a 1-D list of camera indices")
+        c = _cov_ints(cameras, "cameras", (n_cams,))
         out.append(np.stack([c, c], 1))
     if pairs is not None:
-        p = ints(pairs, "pairs")
-        if p.ndim != 2 or p.shape[1] != 2:
-            if p.size:
-                raise ValueError("pairs must have shape [m, 2]")
-            p = p.reshape(0, 2)
-        out.append(p)
-    out = np.concatenate(out).astype(np.int32)
+        out.append(_cov_ints(pairs, "pairs", (n_cams, n_cams)))
+    out = np.concatenate(out)
     if len(out) == 0:
         raise ValueError("no covariance block requested")
     return np.ascontiguousarray(out)
+
+
+def cov_points(n_pts, points=None):
+    """The int32 [m] point list of slam_ba_covariance_points: `points` in the
+    caller's numbering (None: every point, 0 .. n_pts - 1; an empty list:
+    none).  An index may repeat.  Raises ValueError on an index outside
+    [0, n_pts), a non-integer or an input that is not 1-D."""
+    n_pts = int(n_pts)
+    if n_pts < 0:
+        raise ValueError("n_pts must be >= 0")
+    if points is None:
+        return np.arange(n_pts, dtype=np.int32)
+    return _cov_ints(points, "points", (n_pts,))
+
+
+def cov_cross(n_pts, n_cams, cross):
+    """The int32 [k, 2] (point, camera) list of slam_ba_covariance_points
+    (None or an empty list: none); the camera need not observe the point.
+    Raises ValueError on a point outside [0, n_pts), a camera outside
+    [0, n_cams), a non-integer or a shape other than [k, 2]."""
+    n_pts, n_cams = int(n_pts), int(n_cams)
+    if n_pts < 0 or n_cams < 1:
+        raise ValueError("n_pts must be >= 0 and n_cams >= 1")
+    if cross is None:
+        return np.zeros((0, 2), np.int32)
+    return _cov_ints(cross, "cross (point, camera)", (n_pts, n_cams))
+
+
+PointCovariance = collections.namedtuple("PointCovariance", "points cross cameras")
 
 
 # ----------------------------------------------------------------------------- planner
@@ -1398,13 +1434,35 @@ class BAProblem:
         without that host check (NaN blocks then; cov_status() reads the
         status of the last call).  A point whose 3x3 block is singular
         without damping counts with a zero inverse, as in the LM steps.
-        Landmark covariances are not computed, and a landmark shard's system
-        is not summed over ranks here.
+        The landmark blocks of the same inverse: point_covariance().  A
+        landmark shard's system is not summed over ranks here.
         Overwrites `sys`: a build_system() made before the call must be
         repeated before solve_step() (iterate* rebuilds anyway); the LM state
         and the parameters are untouched.  The workspace (two dense tiled
         matrices) is allocated on first use and kept."""
         pr = cov_pairs(self.C, cameras, pairs)
+        fac, rank_tol = self._cov_args(scale, rank_tol)
+        s = self._s  # (a BAWindowSet problem: raises once its buffers were reused)
+        dev = self.t["state"].device
+        with torch.cuda.stream(self.stream if self.stream is not None else torch.cuda.current_stream()):
+            self._cov_buffers(dev)
+            tp = torch.from_numpy(pr).to(dev)
+            out = torch.empty((len(pr), 9, 9), dtype=torch.float64, device=dev)
+            _lib.call("slam_ba_covariance", ctypes.byref(s), ptr(tp), len(pr), rank_tol, ptr(out),
+                      ptr(self._cov_ws), self._cov_ws.numel(), ptr(self._cov_status), self._sp())
+            if scale == "residual":
+                fac = self._cov_residual_factor()
+            if fac is not None:
+                out *= fac
+            if device:
+                return out
+            host = out.cpu().numpy()
+        self._cov_raise(rank_tol)
+        return host
+
+    @staticmethod
+    def _cov_args(scale, rank_tol):
+        """(factor or None for "unit" / "residual", rank_tol), checked."""
         if isinstance(scale, str):
             if scale not in ("unit", "residual"):
                 raise ValueError(f"scale must be 'unit', 'residual' or a positive float, not {scale!r}")
@@ -1416,39 +1474,128 @@ class BAProblem:
         rank_tol = float(rank_tol)
         if not (np.isfinite(rank_tol) and 0.0 <= rank_tol < 1.0):
             raise ValueError(f"rank_tol must be finite and in [0, 1), not {rank_tol!r}")
-        s = self._s  # (a BAWindowSet problem: raises once its buffers were reused)
-        dev = self.t["state"].device
-        with torch.cuda.stream(self.stream if self.stream is not None else torch.cuda.current_stream()):
-            if getattr(self, "_cov_ws", None) is None:
-                n = int(_lib.lib.slam_ba_cov_workspace_len(self.C))
-                self._cov_ws = torch.empty(n, dtype=torch.float64, device=dev)
-                self._cov_status = torch.zeros(1, dtype=torch.int32, device=dev)
-            tp = torch.from_numpy(pr).to(dev)
-            out = torch.empty((len(pr), 9, 9), dtype=torch.float64, device=dev)
-            _lib.call("slam_ba_covariance", ctypes.byref(s), ptr(tp), len(pr), rank_tol, ptr(out),
-                      ptr(self._cov_ws), self._cov_ws.numel(), ptr(self._cov_status), self._sp())
-            if scale == "residual":
-                n_free = 9 * self.C + 3 * self.P
-                if self.fixed is not None:
-                    n_free -= sum(_popcount(int(w) & 0x1FF) for w in self.fixed)
-                dof = 2 * self.O - n_free
-                if dof <= 0:
-                    raise ValueError(f"scale 'residual': 2 O - n_free = {dof} degrees of freedom")
-                fac = 2.0 * self.state()["COST"] / dof
-            if fac is not None:
-                out *= fac
-            if device:
-                return out
-            host = out.cpu().numpy()
+        return fac, rank_tol
+
+    def _cov_buffers(self, dev):
+        if getattr(self, "_cov_ws", None) is None:
+            n = int(_lib.lib.slam_ba_cov_workspace_len(self.C))
+            self._cov_ws = torch.empty(n, dtype=torch.float64, device=dev)
+            self._cov_status = torch.zeros(2, dtype=torch.int32, device=dev)
+
+    def _cov_residual_factor(self):
+        n_free = 9 * self.C + 3 * self.P
+        if self.fixed is not None:
+            n_free -= sum(_popcount(int(w) & 0x1FF) for w in self.fixed)
+        dof = 2 * self.O - n_free
+        if dof <= 0:
+            raise ValueError(f"scale 'residual': 2 O - n_free = {dof} degrees of freedom")
+        return 2.0 * self.state()["COST"] / dof
+
+    def _cov_raise(self, rank_tol):
         if self.cov_status() != 0:
             raise np.linalg.LinAlgError(
                 "BA covariance: the reduced camera system is not positive definite at "
                 f"rank_tol {rank_tol:g} (fix the gauge: hold two cameras whole)")
-        return host
 
     def cov_status(self) -> int:
-        """Status of the last covariance() call: 0 ok, 1 not positive definite."""
-        return int(self._cov_status.item())
+        """Status of the last covariance() / point_covariance() call: 0 ok, 1 not positive definite."""
+        return int(self._cov_status[0].item())
+
+    def cov_undetermined(self) -> int:
+        """Rows of the last point_covariance() call that are NaN because their
+        point is undetermined."""
+        return int(self._cov_status[1].item())
+
+    def point_covariance(self, points=None, cross=None, cameras=None, pairs=None, scale="unit",
+                         rank_tol=1e-8, device=False):
+        """Landmark, landmark-camera and camera blocks of the covariance at the
+        live parameters, from one build and one factorisation: the named tuple
+        PointCovariance(points [m, 3, 3], cross [k, 3, 9], cameras [n, 9, 9]),
+        float64.  They are blocks of (J~^T J~)^-1 over the free parameters, J~
+        the clamped, masked, robust-weighted Jacobian of the LM steps
+        (DESIGN.md 4c).
+        points: point indices in the caller's numbering (cov_points; None:
+        every point, []: none) -> Cov(point, point), exactly symmetric.
+        cross: (point, camera) pairs (cov_cross; None: none) -> Cov(point,
+        camera); the camera need not observe the point; columns of held
+        parameters are exactly 0.
+        cameras, pairs: as covariance(), except that None, None asks for no
+        camera block.  An index may repeat in any list.
+        scale, rank_tol, device and the LinAlgError on a reduced camera system
+        that is not positive definite: as covariance().  A point is
+        undetermined when a pivot of the 3x3 Cholesky of its V = sum Jp^T Jp
+        is not finite or <= rank_tol V_kk (no or one observation, rays nearly
+        parallel): its rows are NaN, cov_undetermined() counts them, nothing
+        is raised.  (The camera blocks still see such a point as the LM steps
+        do: leave one-observation points out of a problem whose camera
+        covariance matters.)  Overwrites `sys` like covariance()."""
+        inv = None
+        if self.perm is not None:  # device point k = caller's point perm[k]
+            inv = np.empty(self.P, np.int32)
+            inv[self.perm] = np.arange(self.P, dtype=np.int32)
+        every = points is None and inv is None
+        pts = cov_points(self.P, points)
+        cr = cov_cross(self.P, self.C, cross)
+        if inv is not None:
+            pts = inv[pts]
+            cr = np.stack([inv[cr[:, 0]], cr[:, 1]], 1)
+        n_cam_req = sum(0 if x is None else np.size(x) for x in (cameras, pairs))
+        pr = cov_pairs(self.C, cameras, pairs) if n_cam_req else np.zeros((0, 2), np.int32)
+        fac, rank_tol = self._cov_args(scale, rank_tol)
+        s = self._s  # (a BAWindowSet problem: raises once its buffers were reused)
+        dev = self.t["state"].device
+        with torch.cuda.stream(self.stream if self.stream is not None else torch.cuda.current_stream()):
+            self._cov_buffers(dev)
+            lists = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (pr, pts, cr)]
+            outs = [torch.empty((len(a),) + shp, dtype=torch.float64, device=dev)
+                    for a, shp in ((pr, (9, 9)), (pts, (3, 3)), (cr, (3, 9)))]
+            if len(pr) + len(pts) + len(cr):
+                lp = [ptr(t) if t.numel() else None for t in lists]
+                if every:
+                    lp[1] = None  # the all-points form: no list
+                _lib.call("slam_ba_covariance_points", ctypes.byref(s), lp[0], len(pr), ptr(outs[0]),
+                          lp[1], len(pts), ptr(outs[1]), lp[2], len(cr), ptr(outs[2]), rank_tol,
+                          ptr(self._cov_ws), self._cov_ws.numel(), ptr(self._cov_status), self._sp())
+            else:
+                self._cov_status.zero_()
+            if scale == "residual":
+                fac = self._cov_residual_factor()
+            if fac is not None:
+                for o in outs:
+                    o *= fac
+            if not device:
+                outs = [o.cpu().numpy() for o in outs]
+        if not device:
+            self._cov_raise(rank_tol)
+        return PointCovariance(outs[1], outs[2], outs[0])
+
+    def reprojection_covariance(self, points, cameras):
+        """[m, 2, 2]: the covariance of the predicted pixel of point points[i]
+        in camera cameras[i] at the live parameters, A [S_cc S_cp; S_pc S_pp] A^T
+        with A = (A_c | A_p) the raw 2 x 12 Jacobian of the projection (no
+        clamp, no mask, no robust weight) and the blocks of one
+        point_covariance() call (unit scale).  The camera need not observe the
+        point.  Exactly symmetric; NaN for an undetermined point."""
+        pts = cov_points(self.P, points)
+        cam = _cov_ints(cameras, "cameras", (self.C,))
+        if len(pts) != len(cam):
+            raise ValueError("points and cameras must have the same length")
+        if len(pts) == 0:
+            return np.zeros((0, 2, 2))
+        cov = self.point_covariance(points=pts, cross=np.stack([pts, cam], 1), cameras=cam)
+        lc, lp = self.params()
+        # q = the projection itself: the residual is 0 and the clamp inactive
+        q = residuals(lc, lp, cam, pts, np.zeros((len(pts), 2)))
+        r, A = residuals(lc, lp, cam, pts, q, jacobian=True)
+        if np.any(r != 0.0):  # the first pass was clamped (a pixel beyond 5000): one more step
+            q = q + r
+            r, A = residuals(lc, lp, cam, pts, q, jacobian=True)
+        S = np.empty((len(pts), 12, 12))
+        S[:, :9, :9], S[:, 9:, 9:] = cov.cameras, cov.points
+        S[:, 9:, :9] = cov.cross
+        S[:, :9, 9:] = cov.cross.transpose(0, 2, 1)
+        R = A @ S @ A.transpose(0, 2, 1)
+        return 0.5 * (R + R.transpose(0, 2, 1))
 
     def solve(self, max_iters=100, ftol=1e-10, check_every=5):
         """Iterate until a batch of `check_every` iterations that accepted at
@@ -1552,6 +1699,13 @@ class BABatch:
         """BAProblem.covariance of every problem, one after the other (a host
         loop: not a per-iteration path); a list, one entry per problem."""
         return [p.covariance(cameras, pairs, scale, rank_tol, device) for p in self.problems]
+
+    def point_covariance(self, points=None, cross=None, cameras=None, pairs=None, scale="unit",
+                         rank_tol=1e-8, device=False):
+        """BAProblem.point_covariance of every problem, one after the other; a
+        list of PointCovariance, one per problem (the same request for each)."""
+        return [p.point_covariance(points, cross, cameras, pairs, scale, rank_tol, device)
+                for p in self.problems]
 
 
 # ----------------------------------------------------------------------------- kernels
