@@ -715,6 +715,65 @@ long long slam_pose_chain_workspace_len(int n_frames);
 int slam_pose_chain_trf(double* ws, int n_frames, int loop, int max_iter, int first, double ftol,
                         double xtol, double gtol, int max_nfev, double* state, void* stream);
 
+/* ------------------------------------------------------------------ SE(3) pose graph
+ * A general pose graph: N poses x_i = [r (Rodrigues vector), t],
+ * T_i = [R(r_i) | t_i], and E relative-pose edges k = (i, j, z_k, A_k), i != j
+ * in either order, repeated pairs allowed.  z_k = [r_z, t_z] measures
+ * T_i^-1 T_j; A_k is a 6x6 row-major square-root information matrix (the
+ * edge's information is A_k^T A_k).  With E = Z^-1 T_i^-1 T_j the raw residual
+ * is e_k = [Log(R_E); t_E], the weighted one r_k = A_k e_k.  Levenberg-Marquardt
+ * with additive updates on x and the BA's rules and state slots (SLAM_BA_ST_*:
+ * LAMBDA, NU, COST, COST_NEW, PRED, RHO, ACCEPTED, CUR, ITERS, NACCEPT,
+ * CHOL_FAIL); the damped normal equations are factored as a row-profile
+ * ("skyline") Cholesky over 64x64 f64 tiles of 10 poses each, in keyframe
+ * order.  Asynchronous on the caller's stream, no allocation. */
+typedef struct slam_pg_problem {
+  int32_t n_poses, n_edges;
+  int32_t loss;                 /* 0 linear, 1 huber, 2 soft_l1, 3 cauchy, on s = |r_k|^2 (as slam_ba_problem.loss) */
+  int32_t sched_len;            /* ints in sched / sched_host */
+  double loss_scale;            /* delta of `loss` (read when loss != 0) */
+  double* poses[2];             /* [6 N] each; state[SLAM_BA_ST_CUR] names the live one */
+  const int32_t* edge_ij;       /* device [2 E]: i, j per edge */
+  const int32_t* edge_ij_host;  /* the same on the host (validated before any launch) */
+  const double* meas;           /* device [6 E] */
+  const double* sqrt_info;      /* device [36 E] */
+  const uint32_t* pose_fixed;   /* device [N] or null: bit p holds parameter p (0x3F: the pose whole);
+                                 * that column leaves every Jacobian, its step is an exact zero and its
+                                 * value is copied, bit for bit, into the trial buffer */
+  /* The host-built schedule (slam355.posegraph.pg_schedule), a device and a
+   * host copy; the host copy is validated against edge_ij_host before any
+   * launch.  Header of 16 ints: magic 0x50473031, N, E, T = ceil(N / 10), the
+   * unique unordered pose pairs P, the stored tiles, the total panel rows, the
+   * total update pairs, the largest panel and update list of a column.  Then
+   * first[T] (the smallest tile column of tile row I), rowoff[T + 1] (tile
+   * (I, J) is stored tile rowoff[I] + J - first[I]), pose_ptr[N + 1] and
+   * pose_ent[2 E] (pose -> 2 edge + side in edge order), pair_ptr[P + 1],
+   * pair_ij[2 P] (lo < hi, sorted) and pair_ent[E] (2 edge + (i > j) in edge
+   * order), col_ptr[T + 1], upd_ptr[T + 1], the panel rows {I > k : first[I]
+   * <= k} of every column k (ascending) and its update pairs (I, J), I >= J,
+   * over those rows. */
+  const int32_t* sched;
+  const int32_t* sched_host;
+  double* ws;                   /* slam_pg_workspace_len doubles */
+  long long ws_len;
+  double* state;                /* [SLAM_BA_ST_SLOTS] */
+} slam_pg_problem;
+int slam_pg_problem_size(void);
+/* Doubles of ws for N poses, E edges and the schedule's stored tile count. */
+long long slam_pg_workspace_len(int n_poses, int n_edges, int n_tiles_stored);
+/* state <- (lambda0, nu = 2, CUR = 0, COST at poses[0]). */
+int slam_pg_reset(const slam_pg_problem* prob, double lambda0, void* stream);
+/* n_iters LM iterations with no host synchronisation.  A factor that is not
+ * positive definite sets CHOL_FAIL = 1 and takes a zero step (rejected). */
+int slam_pg_iterate(const slam_pg_problem* prob, int n_iters, void* stream);
+/* At the live poses: e[E][6] raw and r[E][6] = sqrt(w) A e (either may be
+ * null).  ws and sched may be null here and in slam_pg_jacobian; state may be
+ * null too, and then poses[0] is read. */
+int slam_pg_residual(const slam_pg_problem* prob, double* d_e, double* d_r, void* stream);
+/* At the live poses: Ji[E][6][6], Jj[E][6][6] = sqrt(w) A d e / d x_i, x_j with
+ * the held columns zero. */
+int slam_pg_jacobian(const slam_pg_problem* prob, double* d_Ji, double* d_Jj, void* stream);
+
 /* ------------------------------------------------------------------ BoW
  * Bag-of-words place recognition (bag_of_words.py).  Descriptors are ORB rows
  * (32 bytes, used as float64 features as scikit-learn converts them); K <= 128

@@ -47,6 +47,20 @@ class BAProblemStruct(ctypes.Structure):
 
 _PROB = ctypes.POINTER(BAProblemStruct)
 
+
+class PGProblemStruct(ctypes.Structure):
+    """Mirror of `slam_pg_problem` (include/slam355.h)."""
+    _fields_ = [
+        ("n_poses", c_i32), ("n_edges", c_i32), ("loss", c_i32), ("sched_len", c_i32),
+        ("loss_scale", ctypes.c_double), ("poses", c_p * 2),
+        ("edge_ij", c_p), ("edge_ij_host", c_p), ("meas", c_p), ("sqrt_info", c_p),
+        ("pose_fixed", c_p), ("sched", c_p), ("sched_host", c_p),
+        ("ws", c_p), ("ws_len", ctypes.c_longlong), ("state", c_p),
+    ]
+
+
+_PG = ctypes.POINTER(PGProblemStruct)
+
 PLAN_TABLES = ("perm", "order", "obs_cam", "obs_pt", "pt_ptr", "grp_ptr", "grp_cslot", "cslot_cam",
                "grp_bslot", "bslot_blk", "blocks", "cam_cslot_ptr", "cslot_row", "blk_bslot_ptr",
                "bslot_row", "sg_ptr", "sg_meta", "sg_cams", "obs_la", "chk_cobs", "obs_meta",
@@ -127,6 +141,12 @@ SIGNATURES = {
     "slam_bow_query": [c_p, c_int, c_p, c_p, c_int, c_p, c_p, c_p],
     "slam_bow_lloyd": [c_p, c_int, c_p, c_p, c_int, c_int, c_p, c_p, c_p],
     "slam_pose_chain_workspace_len": [c_int],
+    "slam_pg_problem_size": [],
+    "slam_pg_workspace_len": [c_int, c_int, c_int],
+    "slam_pg_reset": [_PG, c_double, c_p],
+    "slam_pg_iterate": [_PG, c_int, c_p],
+    "slam_pg_residual": [_PG, c_p, c_p, c_p],
+    "slam_pg_jacobian": [_PG, c_p, c_p, c_p],
     "slam_fast_tiles_workspace_bytes": [c_int, c_int, c_int, c_int, c_int, c_int,
                                         ctypes.POINTER(c_size_t)],
     "slam_fast_tiles": [c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_p,
@@ -165,7 +185,8 @@ _RESTYPE = {"slam_last_error": ctypes.c_char_p, "slam_ba_sys_len": ctypes.c_long
             "slam_pnp_workspace_len": ctypes.c_longlong,
             "slam_pnp_scratch_len": ctypes.c_longlong,
             "slam_fundamental_workspace_len": ctypes.c_longlong,
-            "slam_pose_chain_workspace_len": ctypes.c_longlong}
+            "slam_pose_chain_workspace_len": ctypes.c_longlong,
+            "slam_pg_workspace_len": ctypes.c_longlong}
 
 
 class SlamError(RuntimeError):

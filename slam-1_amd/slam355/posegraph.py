@@ -10,8 +10,18 @@ loop (end pose = start pose), with scipy's TRF.  Here:
   PoseChain                      device-resident TRF (x_scale='jac', exact
                                  trust-region subproblem, analytic Jacobian)
 The drop-in names live in slam355.BundleAdjustment.
+
+The general SE(3) pose graph (csrc/posegraph_se3.hip) is beside
+it: weighted relative-pose edges between arbitrary keyframes, LM on the device
+over a skyline tile Cholesky:
+  PoseGraph                      the device-resident graph and its LM
+  pg_schedule                    the host-built schedule of the skyline factor
+  relative_pose                  the measurement an edge stores
+  edges_from_ba                  weighted edges from a refined BA window
 """
 from __future__ import annotations
+
+import ctypes
 
 import numpy as np
 import torch
@@ -83,3 +93,311 @@ class PoseChain:
 
     def params(self) -> np.ndarray:
         return self.ws[: 6 * self.m].cpu().numpy().copy()
+
+
+# ----------------------------------------------------------------------------- SE(3) pose graph
+PG_MAGIC = 0x50473031
+PG_HDR = 16
+PG_TILE_POSES = 10  # poses per 64x64 tile (60 rows, 4 of padding)
+ST = dict(LAMBDA=0, NU=1, COST=2, COST_NEW=3, PRED=4, RHO=5, ACCEPTED=6, CUR=7, ITERS=8, NACCEPT=9,
+          CHOL_FAIL=11)  # SLAM_BA_ST_*
+FIXED_POSE = 0x3F
+
+
+def _check_edges(n_poses, edges):
+    e = np.asarray(edges)
+    if e.ndim != 2 or e.shape[1] != 2 or len(e) == 0 or not np.issubdtype(e.dtype, np.integer):
+        raise ValueError("edges must be a non-empty integer array [E, 2]")
+    if n_poses < 1 or e.min() < 0 or e.max() >= n_poses:
+        raise ValueError("edge index outside [0, n_poses)")
+    if np.any(e[:, 0] == e[:, 1]):
+        raise ValueError("an edge joins a pose to itself")
+    return np.ascontiguousarray(e, np.int32)
+
+
+def pg_tables(n_poses, edges, full=False):
+    """The tables of the skyline schedule as a dict (pg_schedule packs them):
+    first[T], rowoff[T + 1], pose_ptr / pose_ent (pose -> 2 edge + side, edge
+    order), pair_ptr / pair_ij / pair_ent (sorted unique (lo, hi) -> 2 edge +
+    (i > j), edge order), col_ptr / rows (panel rows {I > k : first[I] <= k}
+    of column k, ascending), upd_ptr / upd (its update pairs (I, J), I >= J,
+    over those rows).  Tiles hold PG_TILE_POSES poses in keyframe order; tile
+    row I stores the columns first[I]..I.  full: first[I] = 0 (the dense lower
+    triangle, for comparison)."""
+    e = _check_edges(n_poses, edges)
+    N, E = int(n_poses), len(e)
+    T = (N + PG_TILE_POSES - 1) // PG_TILE_POSES
+    lo, hi = e.min(1), e.max(1)
+    first = np.arange(T, dtype=np.int64)
+    if full:
+        first[:] = 0
+    else:
+        np.minimum.at(first, hi // PG_TILE_POSES, lo // PG_TILE_POSES)
+    rowoff = np.concatenate([[0], np.cumsum(np.arange(T) - first + 1)])
+    # pose -> (edge, side): a stable sort of the 2 E entries by pose keeps edge order
+    ent = np.arange(2 * E)
+    order = np.argsort(e.ravel(), kind="stable")
+    pose_ptr = np.concatenate([[0], np.cumsum(np.bincount(e.ravel(), minlength=N))])
+    pose_ent = ent[order]
+    key = lo.astype(np.int64) * N + hi
+    uk, inv = np.unique(key, return_inverse=True)
+    P = len(uk)
+    porder = np.argsort(inv, kind="stable")
+    pair_ptr = np.concatenate([[0], np.cumsum(np.bincount(inv, minlength=P))])
+    pair_ij = np.stack([uk // N, uk % N], 1)
+    pair_ent = 2 * porder + (e[porder, 0] > e[porder, 1])
+    col_ptr, upd_ptr, rows, upd = [0], [0], [], []
+    for k in range(T):
+        rk = [I for I in range(k + 1, T) if first[I] <= k]
+        rows += rk
+        upd += [(I, J) for a, I in enumerate(rk) for J in rk[: a + 1]]
+        col_ptr.append(len(rows))
+        upd_ptr.append(len(upd))
+    i32 = lambda a: np.asarray(a, np.int32).reshape(-1)  # noqa: E731
+    return dict(N=N, E=E, T=T, P=P, n_tiles=int(rowoff[-1]), first=i32(first), rowoff=i32(rowoff),
+                pose_ptr=i32(pose_ptr), pose_ent=i32(pose_ent), pair_ptr=i32(pair_ptr),
+                pair_ij=i32(pair_ij), pair_ent=i32(pair_ent), col_ptr=i32(col_ptr), upd_ptr=i32(upd_ptr),
+                rows=i32(rows), upd=i32(upd))
+
+
+def pg_schedule(n_poses, edges, full=False):
+    """The int32 schedule of slam_pg_problem.sched (layout: include/slam355.h)."""
+    t = pg_tables(n_poses, edges, full)
+    m = np.diff(t["col_ptr"])
+    hdr = np.zeros(PG_HDR, np.int32)
+    hdr[:10] = [PG_MAGIC, t["N"], t["E"], t["T"], t["P"], t["n_tiles"], len(t["rows"]), len(t["upd"]) // 2,
+                m.max(initial=0), (m * (m + 1) // 2).max(initial=0)]
+    return np.concatenate([hdr] + [t[k] for k in ("first", "rowoff", "pose_ptr", "pose_ent", "pair_ptr", "pair_ij",
+                                                  "pair_ent", "col_ptr", "upd_ptr", "rows", "upd")])
+
+
+# host SO(3) helpers (edges_from_ba's propagation; the device code has its own)
+def _hat(v):
+    return np.array([[0.0, -v[2], v[1]], [v[2], 0.0, -v[0]], [-v[1], v[0], 0.0]])
+
+
+def _so3_exp(r):
+    t2 = float(r @ r)
+    th = np.sqrt(t2)
+    a = 1.0 - t2 / 6.0 if th < 1e-4 else np.sin(th) / th
+    b = 0.5 - t2 / 24.0 if th < 1e-4 else 2.0 * np.sin(0.5 * th) ** 2 / t2
+    K = _hat(r)
+    return np.eye(3) + a * K + b * (K @ K)
+
+
+def _so3_jr(r):
+    t2 = float(r @ r)
+    th = np.sqrt(t2)
+    b = 0.5 - t2 / 24.0 if th < 1e-4 else 2.0 * np.sin(0.5 * th) ** 2 / t2
+    c = 1.0 / 6.0 - t2 / 120.0 if th < 1e-4 else (th - np.sin(th)) / (t2 * th)
+    K = _hat(r)
+    return np.eye(3) - b * K + c * (K @ K)
+
+
+def _so3_jr_inv(r):
+    t2 = float(r @ r)
+    th = np.sqrt(t2)
+    k = 1.0 / 12.0 + t2 / 720.0 if th < 1e-4 else (1.0 - 0.5 * th / np.tan(0.5 * th)) / t2
+    K = _hat(r)
+    return np.eye(3) + 0.5 * K + k * (K @ K)
+
+
+def _so3_log(R):
+    v = 0.5 * np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    s, c = np.linalg.norm(v), 0.5 * (np.trace(R) - 1.0)
+    th = np.arctan2(s, c)
+    if c < 0.0 and s < 1e-3:  # at pi: the axis from the symmetric part
+        w, V = np.linalg.eigh(0.5 * (R + R.T))
+        n = V[:, -1]
+        return th * (n if v @ n >= 0.0 else -n)
+    return v * (1.0 + s * s / 6.0 if s < 1e-4 and c > 0 else th / s)
+
+
+def relative_pose(x_i, x_j):
+    """The 6-vector [r, t] of T_i^-1 T_j for poses x = [r (Rodrigues), t], T =
+    [R(r) | t]: the measurement a PoseGraph edge (i, j) stores."""
+    x_i, x_j = np.asarray(x_i, np.float64), np.asarray(x_j, np.float64)
+    Ri = _so3_exp(x_i[:3])
+    return np.concatenate([_so3_log(Ri.T @ _so3_exp(x_j[:3])), Ri.T @ (x_j[3:6] - x_i[3:6])])
+
+
+def relative_pose_jacobian(x_i, x_j):
+    """d relative_pose / d [x_i, x_j]: [6, 12] (the edge Jacobian at Z = I)."""
+    x_i, x_j = np.asarray(x_i, np.float64), np.asarray(x_j, np.float64)
+    Ri, Rj = _so3_exp(x_i[:3]), _so3_exp(x_j[:3])
+    z = relative_pose(x_i, x_j)
+    Jinv = _so3_jr_inv(z[:3])
+    G = np.zeros((6, 12))
+    G[:3, :3] = -Jinv @ Rj.T @ Ri @ _so3_jr(x_i[:3])
+    G[:3, 6:9] = Jinv @ _so3_jr(x_j[:3])
+    G[3:, :3] = _hat(z[3:]) @ _so3_jr(x_i[:3])
+    G[3:, 3:6] = -Ri.T
+    G[3:, 9:12] = Ri.T
+    return G
+
+
+def edges_from_ba(problem, pairs, scale="unit", rank_tol=1e-8):
+    """Weighted pose-graph edges from a refined BA window: for each keyframe
+    pair (a, b) of `pairs` [m, 2] of a BAProblem (or a BAWindowSet window) the
+    measurement z = relative_pose(x_a, x_b) at the live cameras and its 6x6
+    information matrix, the inverse of the first-order covariance G [Saa Sab;
+    Sab^T Sbb] G^T with G = relative_pose_jacobian and the 6x6 pose blocks of
+    problem.covariance(cameras, pairs, scale).
+
+    Pose convention: an edge's poses are the BAL cameras' own [r, t], i.e.
+    world -> camera (x_cam = R(r) X + t, T = [R | t]); no conversion is made,
+    f, k1, k2 are marginalised by dropping their rows.  A PoseGraph over these
+    edges therefore takes cams[:, :6] as its poses, and z is the transform
+    camera b -> camera a composed as T_a^-1 T_b in that convention.
+    Returns (edges int32 [m, 2], meas [m, 6], information [m, 6, 6]).  Raises
+    np.linalg.LinAlgError where covariance() does, and when a propagated
+    covariance is not positive definite (a pair of held cameras)."""
+    pr = np.asarray(pairs)
+    if pr.ndim != 2 or pr.shape[1] != 2 or len(pr) == 0:
+        raise ValueError("pairs must be a non-empty [m, 2] list of keyframe pairs")
+    if np.any(pr[:, 0] == pr[:, 1]):
+        raise ValueError("a pair joins a keyframe to itself")
+    cams = problem.params()[0]
+    uniq = np.unique(pr)
+    cov = problem.covariance(cameras=uniq, pairs=pr, scale=scale, rank_tol=rank_tol)
+    own = {int(c): cov[q][:6, :6] for q, c in enumerate(uniq)}
+    meas, info = np.zeros((len(pr), 6)), np.zeros((len(pr), 6, 6))
+    for q, (a, b) in enumerate(pr):
+        xa, xb = cams[a, :6], cams[b, :6]
+        Sab = cov[len(uniq) + q][:6, :6]
+        S = np.block([[own[int(a)], Sab], [Sab.T, own[int(b)]]])
+        G = relative_pose_jacobian(xa, xb)
+        Sz = G @ S @ G.T
+        Sz = 0.5 * (Sz + Sz.T)
+        np.linalg.cholesky(Sz)  # LinAlgError when not positive definite
+        meas[q] = relative_pose(xa, xb)
+        info[q] = np.linalg.inv(Sz)
+    return np.ascontiguousarray(pr, np.int32), meas, info
+
+
+class PoseGraph:
+    """A device-resident SE(3) pose graph and its Levenberg-Marquardt.
+
+    poses [N, 6]: x_i = [r (Rodrigues vector), t], T_i = [R(r_i) | t_i].
+    edges [E, 2], meas [E, 6]: edge k = (i, j) measures z_k = T_i^-1 T_j
+    (relative_pose); i != j in either order, repeated pairs allowed.
+    information [E, 6, 6] (factored here: the upper Cholesky factor A with A^T
+    A = information; LinAlgError when one is not positive definite) or
+    sqrt_information [E, 6, 6] = A directly; neither: identity.  fixed: None,
+    or one word per pose (bit p holds parameter p, FIXED_POSE the pose whole),
+    or a bool [N, 6].  The gauge is the caller's: hold one pose.  loss,
+    f_scale: as BAProblem's, on s = |A_k e_k|^2 per edge."""
+
+    def __init__(self, poses, edges, meas, information=None, sqrt_information=None, fixed=None,
+                 loss="linear", f_scale=1.0, stream=None, lam0=1e-4, _full_profile=False):
+        from .ba import loss_args
+
+        dev = require_gpu()
+        x = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1, 6))
+        self.N = len(x)
+        e = _check_edges(self.N, edges)
+        self.E = len(e)
+        z = np.ascontiguousarray(np.asarray(meas, np.float64).reshape(-1, 6))
+        if len(z) != self.E:
+            raise ValueError("meas must hold 6 values per edge")
+        if information is not None and sqrt_information is not None:
+            raise ValueError("give information or sqrt_information, not both")
+        if information is not None:
+            info = np.asarray(information, np.float64).reshape(self.E, 6, 6)
+            A = np.stack([np.linalg.cholesky(m).T for m in info])
+        elif sqrt_information is not None:
+            A = np.asarray(sqrt_information, np.float64).reshape(self.E, 6, 6)
+        else:
+            A = np.tile(np.eye(6), (self.E, 1, 1))
+        if not (np.all(np.isfinite(x)) and np.all(np.isfinite(z)) and np.all(np.isfinite(A))):
+            raise ValueError("poses, meas and the information must be finite")
+        code, scale = loss_args(loss, f_scale)
+        words = None
+        if fixed is not None:
+            f = np.asarray(fixed)
+            if f.dtype == bool:
+                f = (f.reshape(self.N, 6).astype(np.uint32) << np.arange(6, dtype=np.uint32)).sum(1)
+            if f.shape != (self.N,) or np.any(f < 0) or np.any(f > FIXED_POSE):
+                raise ValueError("fixed: one word in [0, 0x3F] per pose, or a bool [N, 6]")
+            words = np.ascontiguousarray(f, np.uint32)
+        self.stream = stream
+        self.edges = e
+        self.sched_host = pg_schedule(self.N, e, full=_full_profile)  # kept alive: the library reads it
+        self.n_tiles = int(self.sched_host[5])
+        T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+        n_ws = int(_lib.lib.slam_pg_workspace_len(self.N, self.E, self.n_tiles))
+        self.t = dict(x0=T(x), x1=T(x), edges=T(e), meas=T(z), A=T(A), sched=T(self.sched_host),
+                      ws=torch.zeros(n_ws, dtype=torch.float64, device=dev),
+                      state=torch.zeros(20, dtype=torch.float64, device=dev))
+        if words is not None:
+            self.t["fixed"] = T(words)
+        s = _lib.PGProblemStruct()
+        s.n_poses, s.n_edges, s.loss, s.sched_len = self.N, self.E, code, len(self.sched_host)
+        s.loss_scale = scale
+        s.poses[0], s.poses[1] = self.t["x0"].data_ptr(), self.t["x1"].data_ptr()
+        s.edge_ij, s.edge_ij_host = self.t["edges"].data_ptr(), self.edges.ctypes.data
+        s.meas, s.sqrt_info = self.t["meas"].data_ptr(), self.t["A"].data_ptr()
+        s.pose_fixed = self.t["fixed"].data_ptr() if words is not None else None
+        s.sched, s.sched_host = self.t["sched"].data_ptr(), self.sched_host.ctypes.data
+        s.ws, s.ws_len, s.state = self.t["ws"].data_ptr(), n_ws, self.t["state"].data_ptr()
+        self._s = s
+        self.reset(lam0)
+
+    def _sp(self):
+        return stream_ptr(self.stream)
+
+    def reset(self, lam0=1e-4):
+        """LM state <- (lam0, nu = 2), COST at the first buffer's poses."""
+        _lib.call("slam_pg_reset", ctypes.byref(self._s), float(lam0), self._sp())
+
+    def iterate(self, n: int = 1, lam0=None):
+        """n LM iterations, no host synchronisation (lam0: reset first)."""
+        if lam0 is not None:
+            if self.state()["CUR"] != 0.0:
+                self.t["x0"].copy_(self.t["x1"])
+            self.reset(lam0)
+        _lib.call("slam_pg_iterate", ctypes.byref(self._s), int(n), self._sp())
+
+    def solve(self, max_iter=100, ftol=1e-10, xtol=1e-10, chunk=5) -> dict:
+        """Iterate in chunks of `chunk` until a chunk that accepted a step
+        lowered the cost by less than ftol (relative) or moved no parameter by
+        more than xtol (1 + |x|), until lambda saturates, or max_iter."""
+        done, st = 0, self.state()
+        x = self.poses()
+        while done < max_iter:
+            k = min(chunk, max_iter - done)
+            c0, n0 = st["COST"], st["NACCEPT"]
+            self.iterate(k)
+            done += k
+            st, xn = self.state(), self.poses()
+            if st["LAMBDA"] >= 1e30:
+                break
+            if st["NACCEPT"] > n0 and (abs(c0 - st["COST"]) <= ftol * max(st["COST"], 1e-300)
+                                       or np.max(np.abs(xn - x) / (1.0 + np.abs(x))) <= xtol):
+                break
+            x = xn
+        return st
+
+    def state(self) -> dict:
+        s = self.t["state"].cpu().numpy()
+        return {k: float(s[v]) for k, v in ST.items()}
+
+    def poses(self) -> np.ndarray:
+        """[N, 6] at the live parameters."""
+        cur = int(self.t["state"][ST["CUR"]].item() != 0)
+        return self.t[f"x{cur}"].cpu().numpy().reshape(self.N, 6).copy()
+
+    def residuals(self, weighted=True) -> np.ndarray:
+        """[E, 6] at the live poses: sqrt(w) A e (weighted) or the raw e."""
+        out = torch.empty((self.E, 6), dtype=torch.float64, device=self.t["state"].device)
+        _lib.call("slam_pg_residual", ctypes.byref(self._s), None if weighted else ptr(out),
+                  ptr(out) if weighted else None, self._sp())
+        return out.cpu().numpy()
+
+    def jacobian(self):
+        """(J_i, J_j), [E, 6, 6] each: sqrt(w) A d e / d x_i, x_j, held columns zero."""
+        dev = self.t["state"].device
+        Ji = torch.empty((self.E, 6, 6), dtype=torch.float64, device=dev)
+        Jj = torch.empty_like(Ji)
+        _lib.call("slam_pg_jacobian", ctypes.byref(self._s), ptr(Ji), ptr(Jj), self._sp())
+        return Ji.cpu().numpy(), Jj.cpu().numpy()
