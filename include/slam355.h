@@ -653,6 +653,14 @@ int slam_ba_set_solve_lds_floor(int bytes);
  * linearisation workgroup beside it.  Process-wide (A/B experiments). */
 int slam_orb_set_lds_floor(int bytes);
 
+/* Entries per wave and pyramid level of the corner lists k_orb_tile's FAST pass
+ * leaves for its NMS pass; 0 (default) = the wave's full share of the tile's
+ * scratch (1251 at C2), a larger value is clipped to that.  A level in which a
+ * wave meets more corners than this finds them by scanning the score map
+ * instead, with the same result: a small value forces that path on ordinary
+ * images (tests, profiling).  Process-wide; takes effect at the next launch. */
+int slam_orb_set_corner_cap(int entries_per_wave);
+
 /* *d_min = min(*d_min, d_count[0..n)) on the device (the Tracker's running
  * minimum of slam_orb_tiles' counts: a negative count flags an overflow), with
  * no host round trip. */

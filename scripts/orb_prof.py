@@ -37,6 +37,7 @@ nwg = 5 * imgs.shape[0] * 36
 print(f"ms/launch {ev0.elapsed_time(ev1) / 5:.3f}; cycles per WG {tot / nwg:.0f}")
 for i, n in enumerate(names):
     print(f"  {n:9s} {buf[i] / nwg:9.0f} clk/WG  {100 * buf[i] / tot:5.1f}%")
+print(f"levels (or small-level groups) whose NMS fell back to the map scan: {buf[10]} in {nwg} workgroups")
 print("per level (clk/WG):")
 for lv in range(8):
     row = [buf[16 + 10 * lv + i] / nwg for i in range(10)]

@@ -38,6 +38,7 @@ constexpr int kNMS0 = 29;  // score-map region starts here (needs [30, w-31])
 constexpr int kBl0 = 12;   // blurred region starts here (rotated samples within +-18 of [31, w-32])
 constexpr int kFqW = 320;  // queue entries per wave: < 64 carried + 256 appended per pass
 constexpr int kFq = (kOrbWG / 64) * kFqW * 4;  // FAST / NMS work queues, bytes
+constexpr int kCtrFb = 8;  // ctr slot: a wave's corner list overflowed, the level's NMS scans the map
 
 __constant__ __attribute__((aligned(16))) int8_t c_pattern[256 * 4];
 
@@ -47,6 +48,7 @@ struct OrbGeom {
   int tcap;       // keypoint slots per tile in the workspace
   int cand_cap;   // NMS candidates per level (global scratch, worst case 1/4 density)
   int list_cap;   // kept keypoints / retainBest(2n) survivors per level (LDS)
+  int corner_cap; // FAST corners per wave and level in the tile's scratch (<= 2 cand_cap / 8)
   int lds_a, lds_u, lds_l, lds_s, lds_m;  // byte offsets of the LDS regions
   int lds_fq, lds_tab;  // FAST queues and resize tables (inside U unless glob)
   int glob;       // level images in global memory (whole images too large for LDS)
@@ -302,7 +304,9 @@ __global__ __launch_bounds__(kOrbWG) __attribute__((amdgpu_waves_per_eu(SLAM_ORB
 
   const int tile = blockIdx.x, b = blockIdx.y;
   const int t = threadIdx.x;
-  const int lane = t & 63, wid = t >> 6;
+  // the wave index in an SGPR: the per-wave loops' counters, queue lengths and
+  // trip tests become scalar code
+  const int lane = t & 63, wid = __builtin_amdgcn_readfirstlane(t >> 6);
   const int ty = tile / g.ntx, tx = tile - ty * g.ntx;
   const int x0 = tx * g.tile_w, y0 = ty * g.tile_h;
   const int shp = g.tile_shape[tile];
@@ -326,7 +330,13 @@ __global__ __launch_bounds__(kOrbWG) __attribute__((amdgpu_waves_per_eu(SLAM_ORB
   uint32_t* gcand = ws_cand + slot * 3 * (size_t)g.cand_cap;
   uint32_t* gsvc = gcand + g.cand_cap;
   float* gsvr = reinterpret_cast<float*>(gsvc + g.cand_cap);
+  // While a level's FAST and NMS run, the survivor thirds (used only after NMS,
+  // and only past list_cap survivors) hold the waves' corner lists: the FAST
+  // drain appends, the same wave's NMS consumes (8 x ccap <= 2 cand_cap entries).
+  uint32_t* cl = gsvc + wid * g.corner_cap;
+  const int ccap = g.corner_cap;
 
+  if (t == 0) ctr[kCtrFb] = 0;  // published by the staging barrier
   ORB_T0();
 #ifdef SLAM_ORB_PROFILE
   int orb_lv = 0;
@@ -451,8 +461,9 @@ __global__ __launch_bounds__(kOrbWG) __attribute__((amdgpu_waves_per_eu(SLAM_ORB
     uint8_t* Smap = U;
     const uint32_t mS4 = div_magic(SW4);
     // Four pixels per pass: the 20 quick-reject reads of the group are all
-    // issued before any Smap store.  Survivors (~8% of pixels, but present
-    // in ~30% of waves) are queued in a wave-private LDS list (the tail of
+    // issued before any Smap store.  Quick-reject survivors (24 % of pixels
+    // on the bench's corridor frames, up to 67 % in a patch; FAST corners are
+    // 8.6 %, up to 25.5 %) are queued in a wave-private LDS list (the tail of
     // U past the score map) and take the full test packed 64 per pass
     // instead of diverging inside every wave that holds one.
     // One dword of the map (4 adjacent pixels) per lane and pass: the centre
@@ -462,6 +473,7 @@ __global__ __launch_bounds__(kOrbWG) __attribute__((amdgpu_waves_per_eu(SLAM_ORB
     const int NG4 = SW4 >> 2, SN4 = NG4 * SHd;
     const uint32_t mG4 = div_magic(NG4);
     uint32_t* fq = reinterpret_cast<uint32_t*>(lds + g.lds_fq) + wid * kFqW;
+    int nc = 0;  // wave-uniform length of the wave's corner list
     auto win4 = [&](int a) {  // bytes a .. a+3 of the level image (any alignment)
       const uint32_t* wp = reinterpret_cast<const uint32_t*>(I + (a & ~3));
       return __builtin_amdgcn_alignbyte(wp[1], wp[0], a & 3);
@@ -470,10 +482,32 @@ __global__ __launch_bounds__(kOrbWG) __attribute__((amdgpu_waves_per_eu(SLAM_ORB
     // waves), the rest after the loop; the trip count is wave-uniform, so every
     // lane of the wave takes part in each drain.  A survivor's score byte is
     // stored after its dword of the map was zeroed (same wave, program order).
-    auto fast_drain = [&](int j0) {
-      const int i = (int)fq[j0 + lane];  // padded-map index: y * SW4 + x
-      const int y = fdiv(i, mS4), x = i - y * SW4;
-      Smap[i] = (uint8_t)fast_full(I + (y + kNMS0) * P + x + kNMS0, P);
+    // A lane whose pixel scores (a FAST corner) inside the NMS border appends
+    // the entry the NMS test consumes, (y << 12) | x in image coordinates, to
+    // the wave's corner list cl (wave-aggregated: ballot, mbcnt, one store per
+    // lane); nc, the list length, stays wave-uniform in a register -- the same
+    // wave consumes the list after the barrier.  All 64 lanes enter; the first
+    // n drain.  Entries past ccap are dropped and only counted: such a wave
+    // raises the level's fallback flag below.
+    auto fast_drain = [&](int j0, int n) {
+      int s = 0, x = 0, y = 0;
+      if (lane < n) {
+        const int i = (int)fq[j0 + lane];  // padded-map index: y * SW4 + x
+        y = fdiv(i, mS4);
+        x = i - y * SW4;
+        s = fast_full(I + (y + kNMS0) * P + x + kNMS0, P);
+        Smap[i] = (uint8_t)s;
+      }
+      // image x = x + 29 in [31, W - 32] <=> x - 2 in [0, SWd - 5]: one unsigned
+      // compare per axis, no short-circuit branches
+      const bool keep = ((int)(s > 0) & (int)((uint32_t)(x - 2) <= (uint32_t)(SWd - 5)) &
+                         (int)((uint32_t)(y - 2) <= (uint32_t)(SHd - 5))) != 0;
+      const uint64_t m = __ballot(keep);
+      const uint32_t pos = (uint32_t)nc + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
+                                                                    __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+      if (keep && pos < (uint32_t)ccap)
+        cl[pos] = (((uint32_t)y << 12) | (uint32_t)x) + (((uint32_t)kNMS0 << 12) | (uint32_t)kNMS0);
+      nc += __popcll(m);
     };
     int nq = 0;  // wave-uniform queue length
     for (int gb = wid * 64;; gb += kOrbWG) {
@@ -516,28 +550,27 @@ __global__ __launch_bounds__(kOrbWG) __attribute__((amdgpu_waves_per_eu(SLAM_ORB
       while (nq >= 64 || (!more && nq > 0)) {
         const int n = min(nq, 64);
         nq -= n;
-        if (lane < n) fast_drain(nq);
+        fast_drain(nq, n);
       }
       if (!more) break;
     }
+    if (nc > ccap && lane == 0) ctr[kCtrFb] = 1;  // (cleared after the last NMS / the staging barrier)
     for (int i = t; i < 256; i += kOrbWG) hist[i] = 0;
     if (t < 8) ctr[t] = 0;
     __syncthreads();
     ORB_T(2);
     ORB_CUT(2);
-    // ---- strict 3x3 NMS + border [31, W-32] -> candidates: one dword of
-    // the score map (4 pixels) per lane; the scored pixels (FAST corners,
-    // ~8 %) are queued in the wave-private list and take the 8-neighbour test
-    // 64 at a time (full waves; the queue carries over passes, the rest is
-    // drained after the loop, whose trip count is wave-uniform).  The candidate
+    const bool scan = ctr[kCtrFb] != 0;  // uniform: some wave's corner list overflowed
+    // ---- strict 3x3 NMS + border [31, W-32] -> candidates: the scored
+    // pixels inside the border (FAST corners) take the 8-neighbour test 64 at
+    // a time, straight from the corner list the FAST drain left.  The candidate
     // order is immaterial: the list is ranked by (response, y, x) below and
     // the histogram is order-free.
     {
       const int CH = H - 2 * kEdge;
       const int NG = SW4 >> 2, NT = CH * NG;
       const uint32_t mG = div_magic(NG);
-      auto nms_drain = [&](int j0) {
-        const uint32_t yx = fq[j0 + lane];
+      auto nms_drain = [&](uint32_t yx) {
         const int yq = (int)(yx >> 12), xq = (int)(yx & 4095u);
         const uint8_t* sp = Smap + (yq - kNMS0) * SW4 + (xq - kNMS0);
         const int s = sp[0];
@@ -548,8 +581,22 @@ __global__ __launch_bounds__(kOrbWG) __attribute__((amdgpu_waves_per_eu(SLAM_ORB
           atomicAdd(&hist[s], 1);
         }
       };
+      // The wave's own corner list, 64 entries at a time, the remainder last
+      // (wave-uniform trip count); the next 64 are read before the current
+      // ones are tested.
+      if (!scan) {
+        uint32_t nx = lane < nc ? cl[lane] : 0u;
+        for (int j0 = 0; j0 < nc; j0 += 64) {
+          const uint32_t e = nx;
+          if (j0 + 64 + lane < nc) nx = cl[j0 + 64 + lane];
+          if (j0 + lane < nc) nms_drain(e);
+        }
+      }
+      // A list overflowed (more than ccap corners in one wave's share, dense
+      // noise): every lane re-reads the map a dword at a time and queues
+      // the scored pixels instead.
       int nq = 0;  // wave-uniform
-      for (int base = wid * 64;; base += kOrbWG) {
+      for (int base = wid * 64; scan; base += kOrbWG) {
         const bool more = base < NT;  // wave-uniform
         const int i = more ? base + lane : NT;
         uint32_t w4 = 0u;
@@ -576,12 +623,16 @@ __global__ __launch_bounds__(kOrbWG) __attribute__((amdgpu_waves_per_eu(SLAM_ORB
         while (nq >= 64 || (!more && nq > 0)) {
           const int n = min(nq, 64);
           nq -= n;
-          if (lane < n) nms_drain(nq);
+          if (lane < n) nms_drain(fq[nq + lane]);
         }
         if (!more) break;
       }
     }
     __syncthreads();
+    if (t == 0) ctr[kCtrFb] = 0;  // every thread has read it; next set: the next FAST
+#ifdef SLAM_ORB_PROFILE
+    if (t == 0 && scan) atomicAdd(&g_orb_prof[10], 1ull);
+#endif
     ORB_T(3);
     ORB_CUT(3);
     const int ncand = ctr[0];
@@ -1047,14 +1098,30 @@ __global__ __launch_bounds__(kOrbWG) __attribute__((amdgpu_waves_per_eu(SLAM_ORB
     // ---- (2) FAST score maps of every level, one pass (as the per-level
     // form; queue entries carry the level in bits 30-31)
     uint32_t* fq = reinterpret_cast<uint32_t*>(lds + g.lds_fq) + wid * kFqW;
+    int nc = 0;  // wave-uniform length of the wave's corner list (all levels of the group)
     {
       const int tot = bSN4[0] + bSN4[1] + bSN4[2] + bSN4[3];
-      auto fast_drain = [&](int j0) {
-        const uint32_t e = fq[j0 + lane];
-        const int j = (int)(e >> 30), i = (int)(e & 0x3FFFFFFFu);
-        const int sw4 = pick4(j, bSW4), P = pick4(j, bP);
-        const int y = fdiv(i, pick4(j, bmS)), x = i - y * sw4;
-        pick4(j, bSm)[i] = (uint8_t)fast_full(pick4(j, bI) + (y + kNMS0) * P + x + kNMS0, P);
+      auto fast_drain = [&](int j0, int n) {  // (appends as the per-level form, level in bits 24-25)
+        int s = 0, x = 0, y = 0, j = 0;
+        if (lane < n) {
+          const uint32_t e = fq[j0 + lane];
+          j = (int)(e >> 30);
+          const int i = (int)(e & 0x3FFFFFFFu);
+          const int sw4 = pick4(j, bSW4), P = pick4(j, bP);
+          y = fdiv(i, pick4(j, bmS));
+          x = i - y * sw4;
+          s = fast_full(pick4(j, bI) + (y + kNMS0) * P + x + kNMS0, P);
+          pick4(j, bSm)[i] = (uint8_t)s;
+        }
+        const bool keep = ((int)(s > 0) & (int)((uint32_t)(x - 2) <= (uint32_t)(pick4(j, bSWd) - 5)) &
+                           (int)((uint32_t)(y - 2) <= (uint32_t)(pick4(j, bH) - 2 * kNMS0 - 5))) != 0;
+        const uint64_t m = __ballot(keep);
+        const uint32_t pos = (uint32_t)nc + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
+                                                                      __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        if (keep && pos < (uint32_t)ccap)
+          cl[pos] = (((uint32_t)j << 24) | ((uint32_t)y << 12) | (uint32_t)x) +
+                    (((uint32_t)kNMS0 << 12) | (uint32_t)kNMS0);
+        nc += __popcll(m);
       };
       int nq = 0;
       for (int gb = wid * 64;; gb += kOrbWG) {
@@ -1101,19 +1168,20 @@ __global__ __launch_bounds__(kOrbWG) __attribute__((amdgpu_waves_per_eu(SLAM_ORB
         while (nq >= 64 || (!more && nq > 0)) {
           const int n = min(nq, 64);
           nq -= n;
-          if (lane < n) fast_drain(nq);
+          fast_drain(nq, n);
         }
         if (!more) break;
       }
     }
+    if (nc > ccap && lane == 0) ctr[kCtrFb] = 1;  // (clear since the last level's NMS barrier)
     __syncthreads();
     ORB_T(2);
+    const bool scan = ctr[kCtrFb] != 0;  // uniform
     // ---- (3) strict 3x3 NMS + border over every level's map, one pass
     // (queue entries: level in bits 24-25, y in 12-22, x in 0-11)
     {
       const int tot = bNT[0] + bNT[1] + bNT[2] + bNT[3];
-      auto nms_drain = [&](int j0) {
-        const uint32_t e = fq[j0 + lane];
+      auto nms_drain = [&](uint32_t e) {
         const int j = (int)(e >> 24);
         const uint32_t yx = e & 0xFFFFFFu;
         const int yq = (int)(yx >> 12), xq = (int)(yx & 4095u);
@@ -1127,8 +1195,16 @@ __global__ __launch_bounds__(kOrbWG) __attribute__((amdgpu_waves_per_eu(SLAM_ORB
           atomicAdd(&hist4[256 * j + s], 1);
         }
       };
+      if (!scan) {  // the wave's own corner list (as the per-level form)
+        uint32_t nx = lane < nc ? cl[lane] : 0u;
+        for (int j0 = 0; j0 < nc; j0 += 64) {
+          const uint32_t e = nx;
+          if (j0 + 64 + lane < nc) nx = cl[j0 + 64 + lane];
+          if (j0 + lane < nc) nms_drain(e);
+        }
+      }
       int nq = 0;
-      for (int base = wid * 64;; base += kOrbWG) {
+      for (int base = wid * 64; scan; base += kOrbWG) {  // a list overflowed: scan the maps
         const bool more = base < tot;  // wave-uniform
         uint32_t w4 = 0u;
         int y = 0, g4 = 0, j = 0;
@@ -1157,12 +1233,15 @@ __global__ __launch_bounds__(kOrbWG) __attribute__((amdgpu_waves_per_eu(SLAM_ORB
         while (nq >= 64 || (!more && nq > 0)) {
           const int n = min(nq, 64);
           nq -= n;
-          if (lane < n) nms_drain(nq);
+          if (lane < n) nms_drain(fq[nq + lane]);
         }
         if (!more) break;
       }
     }
     __syncthreads();
+#ifdef SLAM_ORB_PROFILE
+    if (t == 0 && scan) atomicAdd(&g_orb_prof[10], 1ull);
+#endif
     ORB_T(3);
     // ---- (4) retainBest(2 n_l) thresholds: wave j, level j
     if (wid < NB) {
@@ -1636,6 +1715,8 @@ __global__ __launch_bounds__(64) void k_orb_compact(const float* __restrict__ ws
 }
 
 // ---------------------------------------------------------------- host side
+int g_orb_corner_cap = 0;  // slam_orb_set_corner_cap (0: the scratch's full share)
+
 int build_geom(int H, int W, int stride, int max_kp, int overlap_div, int height_div,
                int width_div, OrbGeom* g) {
   SLAM_REQUIRE(H > 0 && W > 0 && stride >= W, "slam_orb: bad image shape");
@@ -1732,6 +1813,8 @@ int build_geom(int H, int W, int stride, int max_kp, int overlap_div, int height
   for (int l = 0; l < kNLev; ++l) nmax = max(nmax, g->nl[l]);
   g->cand_cap = max(max_cand, 1);
   g->list_cap = max(2 * nmax, nmax + 256);
+  g->corner_cap = 2 * g->cand_cap / (kOrbWG / 64);
+  if (g_orb_corner_cap > 0) g->corner_cap = min(g->corner_cap, g_orb_corner_cap);
   int max_w = 0, max_h = 0;
   for (int s = 0; s < g->nshapes; ++s) {
     max_w = max(max_w, g->sw[s]);
@@ -1834,7 +1917,8 @@ __global__ __launch_bounds__(256) void k_count_min(const int32_t* __restrict__ c
 #ifdef SLAM_ORB_PROFILE
 // phases: 0 stage, 1 resize, 2 FAST map, 3 NMS, 4 retainBest(2n), 5 Harris,
 // 6 rank + retainBest(n), 7 IC angle, 8 blur, 9 rBRIEF + write (cycles summed
-// over workgroups); reads and clears the counters.
+// over workgroups); slot 10 counts the levels (or small-level groups) whose NMS
+// fell back to the map scan; reads and clears the counters.
 extern "C" int slam_orb_profile_read(unsigned long long* out96) {
   SLAM_HIP(hipDeviceSynchronize());
   SLAM_HIP(hipMemcpyFromSymbol(out96, HIP_SYMBOL(g_orb_prof), 96 * sizeof(unsigned long long)));
@@ -1856,6 +1940,12 @@ extern "C" int slam_count_min(const int32_t* d_count, int n, int32_t* d_min, voi
 extern "C" int slam_orb_set_lds_floor(int bytes) {
   SLAM_REQUIRE(bytes >= 0 && bytes <= 160 * 1024, "slam_orb_set_lds_floor: %d B", bytes);
   g_orb_lds_floor = bytes;
+  return SLAM_OK;
+}
+
+extern "C" int slam_orb_set_corner_cap(int entries_per_wave) {
+  SLAM_REQUIRE(entries_per_wave >= 0, "slam_orb_set_corner_cap: %d entries", entries_per_wave);
+  g_orb_corner_cap = entries_per_wave;
   return SLAM_OK;
 }
 

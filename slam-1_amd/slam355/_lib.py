@@ -133,6 +133,7 @@ SIGNATURES = {
                                   c_longlong, c_p, c_p],
     "slam_ba_set_solve_lds_floor": [c_int],
     "slam_orb_set_lds_floor": [c_int],
+    "slam_orb_set_corner_cap": [c_int],
     "slam_count_min": [c_p, c_int, c_p, c_p],
     "slam_hamming_force_valu": [c_int],
     "slam_ba_reset_batch": [_PROB, c_int, c_double, c_p],
