@@ -782,6 +782,63 @@ int slam_pg_residual(const slam_pg_problem* prob, double* d_e, double* d_r, void
  * the held columns zero. */
 int slam_pg_jacobian(const slam_pg_problem* prob, double* d_Ji, double* d_Jj, void* stream);
 
+/* Covariance of the poses: 6x6 blocks of Sigma = H0^-1, where
+ * H0 = J~^T J~ at the live poses with ZERO damping, J~ the robust-weighted,
+ * A-weighted Jacobian without the held columns that every LM step uses -- in
+ * the unit of the edges' information.  d_pairs [n_pairs][2] pose indices
+ * (a, b) with a host copy pairs_host (validated before any launch; the launch
+ * geometry is computed from it); d_cov [n_pairs][6][6] row-major, block q =
+ * Cov(x_a, x_b).  A block with a == b is exactly symmetric; block (a, b) is
+ * block (b, a) transposed bit for bit; an entry may repeat, each gets its own
+ * row, and a row's bits do not depend on the rest of the request or on its
+ * order.  Rows and columns of held parameters (pose_fixed) are +0.0.  The
+ * caller fixes the gauge (one pose held whole suffices): d_status[0] = 1 and
+ * every output NaN when H0 is not numerically positive definite, i.e. a pivot
+ * of the unpivoted skyline Cholesky is not finite or L_rr^2 <= rank_tol *
+ * H0_rr (rank_tol finite, in [0, 1)); 0 otherwise.
+ * With c = max(a, b) / 10 and r = min(a, b) / 10 the tile column and row of a
+ * request, each distinct c costs one 64-column solve through the skyline
+ * factor, forwards from tile row c and backwards down to the smallest r asked
+ * of it; all columns share the launches: the factor's + 2 + at most 2 T + 1,
+ * T = ceil(N / 10), whatever the request.  d_ws: slam_pg_cov_workspace_len(
+ * n_poses, n_cols) doubles for the n_cols distinct tile columns of the request
+ * (T tiles of 64x64 each, and the request's tables), ws_len its length.
+ * Asynchronous on `stream`, no allocation, no host sync.  prob->ws is
+ * overwritten (the edge records, the factor, g, D); the poses and every state
+ * slot, lambda included, are kept, and slam_pg_iterate rebuilds all of ws, so
+ * an iteration after the call is unaffected.
+ * Refused before any launch: everything slam_pg_iterate refuses, a null list,
+ * host list, output, workspace or status, n_pairs <= 0, an index out of range,
+ * rank_tol not finite or outside [0, 1), and a workspace shorter than
+ * slam_pg_cov_workspace_len for the request's columns (SLAM_ERR_WORKSPACE).
+ * slam_pg_cov_workspace_len: SLAM_ERR_ARG unless 1 <= n_cols <= T. */
+long long slam_pg_cov_workspace_len(int n_poses, int n_cols);
+int slam_pg_covariance(const slam_pg_problem* prob, const int32_t* d_pairs, const int32_t* pairs_host,
+                       int n_pairs, double rank_tol, double* d_cov /* [n_pairs][6][6] */,
+                       double* d_ws, long long ws_len, int32_t* d_status, void* stream);
+/* The gate of candidate edges k = (i, j, z_k, A_k), i != j, which need not be
+ * edges of the graph (a loop-closure proposal): with e_k, J_i, J_j the raw
+ * residual and Jacobians of that edge at the live poses (nothing held, no
+ * robust weight, A = I),
+ *   P_k = J_i S_ii J_i^T + J_i S_ij J_j^T + (J_i S_ij J_j^T)^T + J_j S_jj J_j^T
+ * (exactly symmetric) from the blocks S of Sigma above, R_k = (A_k^T A_k)^-1
+ * (d_sqrt_info [n][6][6], null: R = 0), S_k = P_k + R_k and d2_k = e_k^T
+ * S_k^-1 e_k, the squared Mahalanobis distance of the proposal from the graph
+ * (chi^2 with 6 degrees of freedom for a consistent one).  With zero
+ * measurements and no information P_k is the first-order covariance of the
+ * relative pose T_i^-1 T_j.  d_d2 [n], d_P [n][6][6], d_e [n][6]: each may be
+ * null, not all.  A candidate whose S_k fails rank_tol's rule on its own 6x6
+ * Cholesky (both poses held and R = 0), or whose A_k^T A_k is not positive
+ * definite, gets d2 = NaN, and d_status[1] counts them; d_status[0] and the
+ * NaN outputs after a failed factor as above.  The tile columns of a request
+ * are those of both poses of every candidate.  Workspace, stream, what is
+ * overwritten and kept, and the refusals as slam_pg_covariance; also refused:
+ * a candidate with i == j, a null d_meas. */
+int slam_pg_gate(const slam_pg_problem* prob, const int32_t* d_cand_ij, const int32_t* cand_ij_host,
+                 const double* d_meas, const double* d_sqrt_info /* nullable: R = 0 */, int n_cand,
+                 double rank_tol, double* d_d2, double* d_P, double* d_e /* each nullable, not all */,
+                 double* d_ws, long long ws_len, int32_t* d_status /* [2] */, void* stream);
+
 /* ------------------------------------------------------------------ BoW
  * Bag-of-words place recognition (bag_of_words.py).  Descriptors are ORB rows
  * (32 bytes, used as float64 features as scikit-learn converts them); K <= 128

@@ -1,8 +1,13 @@
 """Time per LM iteration of posegraph.PoseGraph (profiles/pose_graph/).
 
-    python scripts/pose_graph_time.py loop500|back500|big5000 [full]
+    python scripts/pose_graph_time.py loop500|back500|big5000 [full|cov]
 
-HIP events around iterate(1), median of 5 after one warm-up; the launch count
+`cov` (profiles/pg_cov/): HIP events around one covariance() call
+for the last pose's block and one for 8 poses spread over the trajectory, median
+of 5 after a warm-up, beside the launch count and the host yardstick of the same
+request (scipy.sparse.linalg.splu of H0 plus the solves for the poses' columns).
+
+Otherwise: HIP events around iterate(1), median of 5 after one warm-up; the launch count
 per iteration and the tiles of the row profile against T (T + 1) / 2.  `full`
 forces the profile full (first[I] = 0): the same kernels without the skyline
 (not at big5000: 125 250 tiles).  Yardsticks that are not the code under test:
@@ -114,8 +119,72 @@ def host_solve_ms(g, lam=1e-4):
     return ms, how
 
 
+def host_cov_ms(g, poses):
+    """The host yardstick of a covariance request: scipy.sparse.linalg.splu of
+    the free H0 (undamped, from the device Jacobians, formed beforehand) plus
+    the solves for the 6 columns of every requested pose; median of 5 after a
+    warm-up.  None without scipy."""
+    try:
+        import scipy.sparse as sp
+        from scipy.sparse.linalg import splu
+    except ImportError:
+        return None, None
+    Ji, Jj = g.jacobian()
+    N, E = g.N, g.E
+    rows = (6 * np.arange(E)[:, None, None] + np.arange(6)[None, :, None]) + np.zeros((1, 1, 6), np.int64)
+    ci = 6 * g.edges[:, 0].astype(np.int64)[:, None, None] + np.arange(6)[None, None, :] + np.zeros((1, 6, 1), np.int64)
+    cj = 6 * g.edges[:, 1].astype(np.int64)[:, None, None] + np.arange(6)[None, None, :] + np.zeros((1, 6, 1), np.int64)
+    J = sp.csr_matrix((np.concatenate([Ji.ravel(), Jj.ravel()]),
+                       (np.concatenate([rows.ravel(), rows.ravel()]), np.concatenate([ci.ravel(), cj.ravel()]))),
+                      shape=(6 * E, 6 * N))
+    H = (J.T @ J).tocsc()[6:, 6:].tocsc()  # pose 0 is held whole
+    rhs = np.zeros((6 * N - 6, 6 * len(poses)))
+    for q, a in enumerate(poses):
+        rhs[6 * (a - 1):6 * a, 6 * q:6 * q + 6] = np.eye(6)
+
+    def solve():
+        return splu(H).solve(rhs)
+
+    solve()
+    ts = []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        x = solve()
+        ts.append(1e3 * (time.perf_counter() - t0))
+    return float(np.median(ts)), x
+
+
+def cov_main(name):
+    """`cov`: one covariance() call for the last pose's block and one for 8 poses
+    spread over the trajectory (8 distinct tile columns), DESIGN.md 4e."""
+    odo, edges, meas, fixed = make(name)
+    g = pg.PoseGraph(odo, edges, meas, fixed=fixed)
+    t = pg.pg_tables(g.N, edges)
+    T = t["T"]
+    factor = 3 + T + int(np.count_nonzero(np.diff(t["upd_ptr"])))
+    out = dict(shape=name, mode="cov", poses=g.N, edges=g.E, T=T, tiles=int(t["n_tiles"]), factor_launches=factor)
+    for tag, poses in (("last", [g.N - 1]), ("spread8", [int(v) for v in np.linspace(g.N // 16, g.N - 1, 8)])):
+        plan = pg.pg_cov_plan(g.N, [(a, a) for a in poses])
+        launches = factor + 2 + (T - int(plan["cols"].min())) + (T - int(plan["low"].min())) + 1
+        ms, all_ms = timed(lambda: g.covariance(poses=poses, device=True))
+        cov = g.covariance(poses=poses)
+        hs, x = host_cov_ms(g, poses)
+        out[tag] = dict(poses=poses, cols=int(len(plan["cols"])), launches=launches, ms=round(ms, 3), ms_all=all_ms,
+                        us_per_launch=round(1e3 * ms / launches, 2), status=g.cov_status())
+        if hs is not None:
+            dev = 0.0
+            for q, a in enumerate(poses):  # the device blocks against the host solve, the tests' measure
+                ref = x[6 * (a - 1):6 * a, 6 * q:6 * q + 6]
+                d = np.sqrt(np.diag(ref))
+                dev = max(dev, float(np.max(np.abs(cov[q] - ref) / np.outer(d, d))))
+            out[tag].update(host_splu_ms=round(hs, 3), deviation_from_host=dev)
+    print(json.dumps(out))
+
+
 def main():
     name = sys.argv[1] if len(sys.argv) > 1 else "loop500"
+    if len(sys.argv) > 2 and sys.argv[2] == "cov":
+        return cov_main(name)
     full = len(sys.argv) > 2 and sys.argv[2] == "full"
     odo, edges, meas, fixed = make(name)
     g = pg.PoseGraph(odo, edges, meas, fixed=fixed, _full_profile=full)

@@ -19,6 +19,8 @@
 //                  pred, and every edge's cost at the trial point
 //   k_pg_decide    fixed-tree sums of both, then the BA's accept / lambda rules
 // Ordering comes from the stream alone: no kernel waits on another workgroup.
+// The covariance of the poses and the gate of candidate edges
+// reuse the factor at lambda = 0: "covariance" below.
 #include "tile_f64.hpp"
 
 #include <algorithm>
@@ -373,6 +375,10 @@ __global__ __launch_bounds__(kTlWG) void k_pg_zero(PgArgs a) {
 
 // blockIdx.x < N: pose i -> H_ii + lambda D_i, g_i, D_i; else pair q -> H_hi,lo.
 // Thread (a, b) of 36 sums its entry over the list in list order, rows m in order.
+// COV (the covariance's factor at lambda = 0): no damping, D <- diag H itself, and
+// an exact 1.0 (in both) on the diagonal of a held parameter, whose row and
+// column are exact zeros.
+template <bool COV>
 __global__ __launch_bounds__(kPgWG) void k_pg_assemble(PgArgs a) {
   const slam_pg_problem& p = a.p;
   const PgSched S(p.n_poses, p.n_edges, a.T, a.P);
@@ -397,9 +403,14 @@ __global__ __launch_bounds__(kPgWG) void k_pg_assemble(PgArgs a) {
       double* tile = p.ws + L.tiles + (long long)(rowoff[I] + I - first[I]) * kTB * kTB;
       const int lr = row - I * kTB;
       if (ea == eb) {
-        const double d = clampd(h);
-        p.ws[L.d + row + ea] = d;
-        h += p.state[SLAM_BA_ST_LAMBDA] * d;
+        if constexpr (COV) {
+          if (p.pose_fixed != nullptr && ((p.pose_fixed[i] >> ea) & 1u)) h = 1.0;
+          p.ws[L.d + row + ea] = h;
+        } else {
+          const double d = clampd(h);
+          p.ws[L.d + row + ea] = d;
+          h += p.state[SLAM_BA_ST_LAMBDA] * d;
+        }
       }
       tile[(lr + ea) * kTB + lr + eb] = h;
     } else if (t < 42) {
@@ -672,6 +683,411 @@ __global__ void k_pg_reset(slam_pg_problem p, double lam0) {
   if (t < SLAM_BA_ST_SLOTS) p.state[t] = t == SLAM_BA_ST_LAMBDA ? lam0 : (t == SLAM_BA_ST_NU ? 2.0 : 0.0);
 }
 
+// ---------------------------------------------------------------- covariance
+// Blocks of Sigma = H0^-1, H0 = J~^T J~ at the live poses with no
+// damping: the factor of the LM step with k_pg_assemble<true>, a rank test of
+// its pivots (k_pg_rank), then per distinct tile column c of the request the
+// 64 columns X = Sigma E_c through the skyline factor, L Y = E_c forwards
+// (k_pg_cov_fwd, tile rows c..T-1) and L^T X = Y backwards (k_pg_cov_bwd, tile
+// rows T-1 down to the lowest one asked of that column), in the caller's
+// workspace; all columns share every launch.  A block (a, b) is read from the
+// column of the larger pose index (k_pg_cov_pick), the relative-pose
+// covariance and the gate of a candidate edge from three of them (k_pg_gate).
+struct PgCovLayout {  // inside d_ws: three int tables of T, then n_cols x T tiles (doubles)
+  long long slot, low, col;  // ints: tile column -> slot or -1; its lowest tile row (T: none); slot -> tile column
+  long long tiles, total;    // doubles
+  __host__ __device__ PgCovLayout(int T, int n_cols) {
+    slot = 0;
+    low = T;
+    col = 2ll * T;
+    tiles = ((3ll * T + 1) / 2 + 7) / 8 * 8;
+    total = tiles + (long long)n_cols * T * kTB * kTB;
+  }
+};
+
+// The request's tables from the device copy of the list: entry (a, b) asks
+// tile column max / 10 down to tile row min / 10 (gate: also both marginal
+// blocks).  Slots in ascending column order; a column past n_cols (a device
+// list that is not the host's) gets none, and its blocks come out NaN.
+__global__ __launch_bounds__(kTlWG) void k_pg_cov_plan(int n_poses, int T, const int32_t* __restrict__ list,
+                                                       int n, int gate, double* cws, int n_cols) {
+  const PgCovLayout C(T, n_cols);
+  int* tab = reinterpret_cast<int*>(cws);
+  const int t = threadIdx.x;
+  for (int q = t; q < T; q += kTlWG) {
+    tab[C.slot + q] = -1;
+    tab[C.low + q] = T;
+    tab[C.col + q] = -1;
+  }
+  __syncthreads();
+  for (int q = t; q < n; q += kTlWG) {
+    const int a = list[2 * q], b = list[2 * q + 1];
+    if ((unsigned)a >= (unsigned)n_poses || (unsigned)b >= (unsigned)n_poses) continue;
+    const int ta = a / kPgTP, tb = b / kPgTP;
+    atomicMin(tab + C.low + max(ta, tb), min(ta, tb));
+    if (gate) atomicMin(tab + C.low + min(ta, tb), min(ta, tb));
+  }
+  __syncthreads();
+  if (t >= 64) return;
+  int run = 0;
+  for (int base = 0; base < T; base += 64) {
+    const int q = base + t;
+    // (an agent-scope load: the minima were formed by atomics, past this CU's L1)
+    const bool need = q < T && __hip_atomic_load(tab + C.low + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < T;
+    const unsigned long long m = __ballot(need);
+    const int s = run + __popcll(m & ((1ull << t) - 1ull));
+    if (need && s < n_cols) {
+      tab[C.slot + q] = s;
+      tab[C.col + s] = q;
+    }
+    run += __popcll(m);
+  }
+}
+
+// Every pivot against the stored diagonal: L_rr = 1 / (L_kk^-1)_rr from dinv,
+// H_rr in D.  status[0] = 1 (and the failure flag raised for the kernels that
+// follow) when the factor failed, a pivot is not finite or L_rr^2 <= rank_tol
+// H_rr; words == 2: status[1] <- 0 for k_pg_gate's count.
+__global__ __launch_bounds__(kTlWG) void k_pg_rank(PgArgs a, double rank_tol, int32_t* __restrict__ status,
+                                                   int words) {
+  const slam_pg_problem& p = a.p;
+  const PgLayout L(p.n_poses, p.n_edges, a.T, a.n_tiles);
+  __shared__ int okf;
+  if (threadIdx.x == 0) okf = pg_failed(p.ws, L) ? 1 : 0;
+  __syncthreads();
+  bool bad = okf != 0;
+  if (!bad) {
+    for (int r = threadIdx.x; r < a.T * kTB; r += kTlWG) {
+      const double xd = p.ws[L.dinv + (long long)(r >> 6) * kTB * kTB + (r & 63) * (kTB + 1)];
+      const double piv = 1.0 / (xd * xd);
+      bad = bad || !(xd > 0.0 && xd < INFINITY) || !(piv < INFINITY) || piv <= rank_tol * p.ws[L.d + r];
+    }
+  }
+  const int any = __syncthreads_or(bad ? 1 : 0);
+  if (threadIdx.x != 0) return;
+  if (any) *reinterpret_cast<int*>(p.ws + L.flag) = 1;
+  status[0] = any ? 1 : 0;
+  if (words == 2) status[1] = 0;
+}
+
+// Forward, tile row k, one workgroup per requested column c (slot blockIdx.x;
+// c > k: nothing yet): Y_c = L_cc^-1, Y_k = -L_kk^-1 sum_{J = max(first[k], c)}^{k-1} L_kJ Y_J.
+__global__ __launch_bounds__(kTlWG) void k_pg_cov_fwd(PgArgs a, double* cws, int n_cols, int k) {
+  const slam_pg_problem& p = a.p;
+  const PgSched S(p.n_poses, p.n_edges, a.T, a.P);
+  const PgLayout L(p.n_poses, p.n_edges, a.T, a.n_tiles);
+  const PgCovLayout C(a.T, n_cols);
+  __shared__ double Xf[kTB * kTB], Yf[kTB * kTB];
+  __shared__ int okf;
+  if (threadIdx.x == 0) okf = pg_failed(p.ws, L) ? 1 : 0;
+  __syncthreads();
+  if (okf != 0) return;
+  const int c = reinterpret_cast<const int*>(cws)[C.col + blockIdx.x];
+  if (c < 0 || c > k) return;
+  double* X = cws + C.tiles + (long long)blockIdx.x * a.T * kTB * kTB;
+  double* Yk = X + (long long)k * kTB * kTB;
+  const double* Vkk = p.ws + L.dinv + (long long)k * kTB * kTB;
+  if (k == c) {
+    for (int e = threadIdx.x; e < kTB * kTB; e += kTlWG) Yk[e] = Vkk[e];
+    return;
+  }
+  const int first = p.sched[S.first + k];
+  const double* Lk = p.ws + L.tiles + (long long)(p.sched[S.rowoff + k] - first) * kTB * kTB;  // tile (k, 0)
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  d4 acc[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) acc[s] = d4{0.0, 0.0, 0.0, 0.0};
+  for (int J = max(first, c); J < k; ++J) {
+    tile_to_frag(Lk + (long long)J * kTB * kTB, kTB, Xf);
+    tile_to_frag_t(X + (long long)J * kTB * kTB, kTB, Yf);
+    __syncthreads();
+    cov_gemm(Xf, Yf, acc);
+    __syncthreads();  // Xf / Yf reloaded next J
+  }
+  tile_to_frag(Vkk, kTB, Xf);
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      Yf[frag_idx(s * 16 + (lane & 15), w * 16 + (lane >> 4) + 4 * r)] = acc[s][r];  // the sum, transposed image
+  __syncthreads();
+#pragma unroll
+  for (int s = 0; s < 4; ++s) acc[s] = d4{0.0, 0.0, 0.0, 0.0};
+  cov_gemm(Xf, Yf, acc, true);
+  cov_store(Yk, kTB, acc);
+}
+
+// Backward, tile row k, one workgroup per requested column (its lowest row >
+// k: done): X_k = L_kk^-T (Y_k - sum_I L_Ik^T X_I), I over column k's panel
+// rows, in place over Y_k (Y_k = 0 above the column's own tile row, unread).
+__global__ __launch_bounds__(kTlWG) void k_pg_cov_bwd(PgArgs a, double* cws, int n_cols, int k) {
+  const slam_pg_problem& p = a.p;
+  const PgSched S(p.n_poses, p.n_edges, a.T, a.P);
+  const PgLayout L(p.n_poses, p.n_edges, a.T, a.n_tiles);
+  const PgCovLayout C(a.T, n_cols);
+  __shared__ double Xf[kTB * kTB], Yf[kTB * kTB];
+  __shared__ int okf;
+  if (threadIdx.x == 0) okf = pg_failed(p.ws, L) ? 1 : 0;
+  __syncthreads();
+  if (okf != 0) return;
+  const int* tab = reinterpret_cast<const int*>(cws);
+  const int c = tab[C.col + blockIdx.x];
+  if (c < 0 || tab[C.low + c] > k) return;
+  const int32_t* first = p.sched + S.first;
+  const int32_t* rowoff = p.sched + S.rowoff;
+  const int r0 = p.sched[S.col_ptr + k], r1 = p.sched[S.col_ptr + k + 1];
+  double* X = cws + C.tiles + (long long)blockIdx.x * a.T * kTB * kTB;
+  double* Xk = X + (long long)k * kTB * kTB;
+  const double* tiles = p.ws + L.tiles;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  d4 acc[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) acc[s] = d4{0.0, 0.0, 0.0, 0.0};
+  for (int u = r0; u < r1; ++u) {
+    const int I = p.sched[S.lists + u];
+    tile_to_frag_t(tiles + (long long)(rowoff[I] + k - first[I]) * kTB * kTB, kTB, Xf);
+    tile_to_frag_t(X + (long long)I * kTB * kTB, kTB, Yf);
+    __syncthreads();
+    cov_gemm(Xf, Yf, acc);
+    __syncthreads();  // Xf / Yf reloaded next I
+  }
+  tile_to_frag_t(p.ws + L.dinv + (long long)k * kTB * kTB, kTB, Xf);
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = w * 16 + (lane >> 4) + 4 * r, col = s * 16 + (lane & 15);
+      const double y = k >= c ? Xk[row * kTB + col] : 0.0;
+      Yf[frag_idx(col, row)] = y - acc[s][r];  // transposed image
+    }
+  __syncthreads();  // (every read of Y_k is done before the stores below)
+#pragma unroll
+  for (int s = 0; s < 4; ++s) acc[s] = d4{0.0, 0.0, 0.0, 0.0};
+  cov_gemm(Xf, Yf, acc);
+  cov_store(Xk, kTB, acc);
+}
+
+// Where Cov(a, b) lies: entry (m, n) = base[m * sr + n * sc], read from the
+// column of the larger pose index (so block (a, b) is block (b, a) transposed
+// bit for bit); base == nullptr: not in the request's tables.
+struct PgBlk {
+  const double* base;
+  int sr, sc;
+};
+__device__ __forceinline__ PgBlk pg_cov_block(const double* cws, const PgCovLayout& C, int T, int n_cols, int a,
+                                              int b) {
+  const int* tab = reinterpret_cast<const int*>(cws);
+  const int lo = min(a, b), hi = max(a, b);
+  const int c = hi / kPgTP, r = lo / kPgTP;
+  const int s = tab[C.slot + c];
+  if (s < 0 || s >= n_cols || tab[C.low + c] > r) return PgBlk{nullptr, 0, 0};
+  const double* tile = cws + C.tiles + ((long long)s * T + r) * kTB * kTB;
+  const double* base = tile + (pg_row(lo) - r * kTB) * kTB + (pg_row(hi) - c * kTB);
+  return a <= b ? PgBlk{base, kTB, 1} : PgBlk{base, 1, kTB};
+}
+__device__ __forceinline__ bool pg_held(const slam_pg_problem& p, int i, int q) {
+  return p.pose_fixed != nullptr && ((p.pose_fixed[i] >> q) & 1u);
+}
+// Entry (m, n) of Cov(a, b): +0.0 on held rows and columns, the lower half
+// mirrored when a == b.
+__device__ __forceinline__ double pg_cov_entry(const slam_pg_problem& p, const PgBlk& B, int a, int b, int m,
+                                               int n) {
+  if (pg_held(p, a, m) || pg_held(p, b, n)) return 0.0;
+  if (a == b) return B.base[max(m, n) * kTB + min(m, n)];
+  return B.base[m * B.sr + n * B.sc];
+}
+
+// One workgroup per requested block: 36 lanes, one entry each.  NaN when the
+// factor failed the rank test.
+__global__ __launch_bounds__(64) void k_pg_cov_pick(PgArgs a, const int32_t* __restrict__ pairs,
+                                                    const double* __restrict__ cws, int n_cols,
+                                                    double* __restrict__ cov) {
+  const slam_pg_problem& p = a.p;
+  const PgLayout L(p.n_poses, p.n_edges, a.T, a.n_tiles);
+  const PgCovLayout C(a.T, n_cols);
+  __shared__ int okf;
+  if (threadIdx.x == 0) okf = pg_failed(p.ws, L) ? 1 : 0;
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t >= 36) return;
+  const int i = pairs[2 * blockIdx.x], j = pairs[2 * blockIdx.x + 1];
+  double v = __builtin_nan("");
+  if (okf == 0 && (unsigned)i < (unsigned)p.n_poses && (unsigned)j < (unsigned)p.n_poses) {
+    const PgBlk B = pg_cov_block(cws, C, a.T, n_cols, i, j);
+    if (B.base != nullptr) v = pg_cov_entry(p, B, i, j, t / 6, t % 6);
+  }
+  cov[36ll * blockIdx.x + t] = v;
+}
+
+// Lower Cholesky of a symmetric 6x6 (full storage, lower half read and
+// overwritten by L).  Pivot rule: bad when not finite or L_rr^2 <= tol * M_rr
+// (tol = 0: not positive).
+__device__ __forceinline__ bool pg_chol6(double M[36], double tol) {
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    const double mjj = M[7 * j];
+    double d = mjj;
+#pragma unroll
+    for (int k = 0; k < j; ++k) d -= M[6 * j + k] * M[6 * j + k];
+    ok = ok && d < INFINITY && d > tol * mjj && d > 0.0;
+    const double l = sqrt(d), il = 1.0 / l;
+    M[7 * j] = l;
+#pragma unroll
+    for (int i = j + 1; i < 6; ++i) {
+      double s = M[6 * i + j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) s -= M[6 * i + k] * M[6 * j + k];
+      M[6 * i + j] = s * il;
+    }
+  }
+  return ok;
+}
+// y <- L^-1 y (lower L in full storage)
+__device__ __forceinline__ void pg_fsub6(const double Lm[36], double y[6]) {
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    double s = y[i];
+#pragma unroll
+    for (int k = 0; k < i; ++k) s -= Lm[6 * i + k] * y[k];
+    y[i] = s / Lm[7 * i];
+  }
+}
+
+// G += f J1 Sigma_ab J2^T (6x6 row-major), Sigma_ab read entry by entry
+__device__ __forceinline__ void pg_jsj(const slam_pg_problem& p, const PgBlk& B, int a, int b, const double J1[36],
+                                       const double J2[36], double f, double G[36]) {
+  double W[36];  // J1 Sigma_ab
+#pragma unroll
+  for (int m = 0; m < 36; ++m) W[m] = 0.0;
+#pragma unroll
+  for (int u = 0; u < 6; ++u)
+#pragma unroll
+    for (int v = 0; v < 6; ++v) {
+      const double sg = pg_cov_entry(p, B, a, b, u, v);
+#pragma unroll
+      for (int m = 0; m < 6; ++m) W[6 * m + v] += J1[6 * m + u] * sg;
+    }
+#pragma unroll
+  for (int m = 0; m < 6; ++m)
+#pragma unroll
+    for (int n = 0; n < 6; ++n) {
+      double s = W[6 * m] * J2[6 * n];
+#pragma unroll
+      for (int v = 1; v < 6; ++v) s += W[6 * m + v] * J2[6 * n + v];
+      G[6 * m + n] += f * s;
+    }
+}
+
+// One lane per candidate edge k = (i, j, z_k, A_k), not required to be an edge
+// of the graph: e, J_i, J_j as k_pg_lin forms them (nothing held, no weight),
+// P = G + G^T with G = J_i S_ii J_i^T / 2 + J_i S_ij J_j^T + J_j S_jj J_j^T / 2
+// (exactly symmetric), R = (A^T A)^-1 (0 without sqrt_info), S = P + R, d2 =
+// e^T S^-1 e by a 6x6 Cholesky under the rank_tol rule; a candidate that fails
+// it (or whose information is not positive definite) gets d2 = NaN and counts
+// in status[1].  Every output NaN after a failed factor.
+__global__ __launch_bounds__(kPgWG) void k_pg_gate(PgArgs a, const int32_t* __restrict__ cand,
+                                                   const double* __restrict__ meas,
+                                                   const double* __restrict__ sqrt_info, int n,
+                                                   const double* __restrict__ cws, int n_cols, double rank_tol,
+                                                   double* __restrict__ od2, double* __restrict__ oP,
+                                                   double* __restrict__ oe, int32_t* __restrict__ status) {
+  const slam_pg_problem& p = a.p;
+  const PgLayout L(p.n_poses, p.n_edges, a.T, a.n_tiles);
+  const PgCovLayout C(a.T, n_cols);
+  __shared__ int okf;
+  if (threadIdx.x == 0) okf = pg_failed(p.ws, L) ? 1 : 0;
+  __syncthreads();
+  const int k = blockIdx.x * kPgWG + threadIdx.x;
+  if (k >= n) return;
+  const double nan = __builtin_nan("");
+  const int i = cand[2 * k], j = cand[2 * k + 1];
+  PgBlk Bii{nullptr, 0, 0}, Bjj{nullptr, 0, 0}, Bij{nullptr, 0, 0};
+  const bool in = (unsigned)i < (unsigned)p.n_poses && (unsigned)j < (unsigned)p.n_poses && i != j;
+  if (okf == 0 && in) {
+    Bii = pg_cov_block(cws, C, a.T, n_cols, i, i);
+    Bjj = pg_cov_block(cws, C, a.T, n_cols, j, j);
+    Bij = pg_cov_block(cws, C, a.T, n_cols, i, j);
+  }
+  if (Bii.base == nullptr || Bjj.base == nullptr || Bij.base == nullptr) {
+    if (od2 != nullptr) od2[k] = nan;
+    if (oP != nullptr)
+      for (int m = 0; m < 36; ++m) oP[36ll * k + m] = nan;
+    if (oe != nullptr)
+      for (int m = 0; m < 6; ++m) oe[6ll * k + m] = nan;
+    return;
+  }
+  const double* x = p.poses[pg_cur(p)];
+  double xi[6], xj[6], z[6], e[6], Ji[36], Jj[36];
+#pragma unroll
+  for (int q = 0; q < 6; ++q) {
+    xi[q] = x[6 * i + q];
+    xj[q] = x[6 * j + q];
+    z[q] = meas[6ll * k + q];
+  }
+  pg_edge_raw<true>(xi, xj, z, 0u, 0u, e, Ji, Jj);
+  double G[36];
+#pragma unroll
+  for (int m = 0; m < 36; ++m) G[m] = 0.0;
+  pg_jsj(p, Bii, i, i, Ji, Ji, 0.5, G);
+  pg_jsj(p, Bij, i, j, Ji, Jj, 1.0, G);
+  pg_jsj(p, Bjj, j, j, Jj, Jj, 0.5, G);
+  double Sm[36];
+#pragma unroll
+  for (int m = 0; m < 6; ++m)
+#pragma unroll
+    for (int q = 0; q <= m; ++q) Sm[6 * m + q] = Sm[6 * q + m] = G[6 * m + q] + G[6 * q + m];
+  if (oe != nullptr)
+#pragma unroll
+    for (int m = 0; m < 6; ++m) oe[6ll * k + m] = e[m];
+  if (oP != nullptr)
+#pragma unroll
+    for (int m = 0; m < 36; ++m) oP[36ll * k + m] = Sm[m];
+  if (od2 == nullptr) return;
+  bool ok = true;
+  if (sqrt_info != nullptr) {
+    // R = (A^T A)^-1 = M^-T M^-1, M the lower factor of A^T A: column q of M^-1 by a forward solve
+    const double* A = sqrt_info + 36ll * k;
+    double M[36];
+#pragma unroll
+    for (int m = 0; m < 6; ++m)
+#pragma unroll
+      for (int q = 0; q <= m; ++q) {
+        double s = A[m] * A[q];
+#pragma unroll
+        for (int r = 1; r < 6; ++r) s += A[6 * r + m] * A[6 * r + q];
+        M[6 * m + q] = M[6 * q + m] = s;
+      }
+    ok = pg_chol6(M, 0.0);
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+      double y[6];
+#pragma unroll
+      for (int m = 0; m < 6; ++m) y[m] = m == q ? 1.0 : 0.0;
+      pg_fsub6(M, y);  // column q of M^-1 (zero above row q)
+#pragma unroll
+      for (int m = 0; m < 6; ++m) G[6 * m + q] = y[m];
+    }
+#pragma unroll
+    for (int m = 0; m < 6; ++m)
+#pragma unroll
+      for (int q = 0; q <= m; ++q) {
+        double s = 0.0;
+#pragma unroll
+        for (int r = m; r < 6; ++r) s += G[6 * r + m] * G[6 * r + q];
+        Sm[6 * m + q] += s;
+        if (q != m) Sm[6 * q + m] = Sm[6 * m + q];
+      }
+  }
+  ok = pg_chol6(Sm, rank_tol) && ok;
+  pg_fsub6(Sm, e);
+  double d2 = e[0] * e[0];
+#pragma unroll
+  for (int q = 1; q < 6; ++q) d2 += e[q] * e[q];
+  if (!ok) atomicAdd(status + 1, 1);
+  od2[k] = ok ? d2 : nan;
+}
+
 // ---------------------------------------------------------------- host
 inline int nblk(int n, int bs) { return (n + bs - 1) / bs; }
 
@@ -795,6 +1211,99 @@ int pg_check(const slam_pg_problem* p, PgArgs* a) {
   return SLAM_OK;
 }
 
+// Linearise, assemble (COV: undamped, for the covariance) and factor: the
+// column sweep of the skyline Cholesky.
+template <bool COV>
+int pg_launch_factor(const PgArgs& a, hipStream_t s) {
+  const slam_pg_problem& p = a.p;
+  const PgSched S(p.n_poses, p.n_edges, a.T, a.P);
+  const PgLayout L(p.n_poses, p.n_edges, a.T, a.n_tiles);
+  const int32_t* cp = p.sched_host + S.col_ptr;
+  const int32_t* up = p.sched_host + S.upd_ptr;
+  double* rec = p.ws + L.rec;
+  k_pg_lin<true><<<nblk(p.n_edges, kPgWG), kPgWG, 0, s>>>(p, nullptr, 0, rec, kPgRec, rec + 6, rec + 42, kPgRec);
+  SLAM_LAUNCHED("k_pg_lin");
+  k_pg_zero<<<(int)a.n_tiles, kTlWG, 0, s>>>(a);
+  SLAM_LAUNCHED("k_pg_zero");
+  k_pg_assemble<COV><<<p.n_poses + a.P, kPgWG, 0, s>>>(a);
+  SLAM_LAUNCHED("k_pg_assemble");
+  for (int k = 0; k < a.T; ++k) {
+    k_pg_panel<<<1 + cp[k + 1] - cp[k], kTlWG, 0, s>>>(a, k);
+    SLAM_LAUNCHED("k_pg_panel");
+    if (up[k + 1] > up[k]) {
+      k_pg_update<<<up[k + 1] - up[k], kTlWG, 0, s>>>(a, k);
+      SLAM_LAUNCHED("k_pg_update");
+    }
+  }
+  return SLAM_OK;
+}
+
+// The launch geometry of a covariance request, from the host copy of its list
+// (k_pg_cov_plan builds the same tables on the device): the distinct tile
+// columns, the first one, and the lowest tile row any of them is asked for.
+struct PgCovGeom {
+  int n_cols, c_min, r_min;
+};
+
+// What slam_pg_covariance and slam_pg_gate refuse, in one place; `gate`: the
+// list holds candidate edges (i != j, both marginal blocks needed too).
+int pg_cov_check(const char* who, const slam_pg_problem* prob, const int32_t* d_list, const int32_t* list_host,
+                 int n, bool gate, double rank_tol, const double* d_ws, long long ws_len, const int32_t* d_status,
+                 PgArgs* a, PgCovGeom* g) {
+  if (int rc = pg_check(prob, a)) return rc;
+  SLAM_REQUIRE(d_list != nullptr && list_host != nullptr && d_ws != nullptr && d_status != nullptr,
+               "%s: null pointer", who);
+  SLAM_REQUIRE(n >= 1, "%s: count %d < 1", who, n);
+  SLAM_REQUIRE(std::isfinite(rank_tol) && rank_tol >= 0.0 && rank_tol < 1.0,
+               "%s: rank_tol %g must be finite and in [0, 1)", who, rank_tol);
+  const int N = prob->n_poses, T = a->T;
+  std::vector<int> low(T, T);
+  for (int q = 0; q < n; ++q) {
+    const int i = list_host[2 * q], j = list_host[2 * q + 1];
+    SLAM_REQUIRE(i >= 0 && i < N && j >= 0 && j < N, "%s: entry %d (%d, %d) out of range", who, q, i, j);
+    SLAM_REQUIRE(!gate || i != j, "%s: candidate %d joins pose %d to itself", who, q, i);
+    const int ti = i / kPgTP, tj = j / kPgTP;
+    low[std::max(ti, tj)] = std::min(low[std::max(ti, tj)], std::min(ti, tj));
+    if (gate) low[std::min(ti, tj)] = std::min(low[std::min(ti, tj)], std::min(ti, tj));
+  }
+  g->n_cols = 0;
+  g->c_min = g->r_min = T;
+  for (int c = 0; c < T; ++c)
+    if (low[c] < T) {
+      g->n_cols += 1;
+      g->c_min = std::min(g->c_min, c);
+      g->r_min = std::min(g->r_min, low[c]);
+    }
+  const long long need = PgCovLayout(T, g->n_cols).total;
+  if (ws_len < need) {
+    slam::set_error("%s: workspace of %lld doubles, slam_pg_cov_workspace_len(%d, %d) gives %lld", who, ws_len, N,
+                    g->n_cols, need);
+    return SLAM_ERR_WORKSPACE;
+  }
+  return SLAM_OK;
+}
+
+// The factor of H0 (the LM step's launches with k_pg_assemble<true>), the
+// request's tables, the rank test, and both sweeps: the factor's launches + 2 +
+// at most 2 T, whatever the request.
+int pg_cov_launch(const PgArgs& a, const PgCovGeom& g, const int32_t* d_list, int n, bool gate, double rank_tol,
+                  double* d_ws, int32_t* d_status, hipStream_t s) {
+  if (int rc = pg_launch_factor<true>(a, s)) return rc;
+  k_pg_cov_plan<<<1, kTlWG, 0, s>>>(a.p.n_poses, a.T, d_list, n, gate ? 1 : 0, d_ws, g.n_cols);
+  SLAM_LAUNCHED("k_pg_cov_plan");
+  k_pg_rank<<<1, kTlWG, 0, s>>>(a, rank_tol, d_status, gate ? 2 : 1);
+  SLAM_LAUNCHED("k_pg_rank");
+  for (int k = g.c_min; k < a.T; ++k) {
+    k_pg_cov_fwd<<<g.n_cols, kTlWG, 0, s>>>(a, d_ws, g.n_cols, k);
+    SLAM_LAUNCHED("k_pg_cov_fwd");
+  }
+  for (int k = a.T - 1; k >= g.r_min; --k) {
+    k_pg_cov_bwd<<<g.n_cols, kTlWG, 0, s>>>(a, d_ws, g.n_cols, k);
+    SLAM_LAUNCHED("k_pg_cov_bwd");
+  }
+  return SLAM_OK;
+}
+
 }  // namespace
 
 extern "C" int slam_pg_problem_size(void) { return (int)sizeof(slam_pg_problem); }
@@ -827,26 +1336,8 @@ extern "C" int slam_pg_iterate(const slam_pg_problem* prob, int n_iters, void* s
   SLAM_REQUIRE(n_iters >= 0, "slam_pg_iterate: n_iters %d", n_iters);
   hipStream_t s = slam::as_stream(stream);
   const slam_pg_problem& p = a.p;
-  const PgSched S(p.n_poses, p.n_edges, a.T, a.P);
-  const PgLayout L(p.n_poses, p.n_edges, a.T, a.n_tiles);
-  const int32_t* cp = p.sched_host + S.col_ptr;
-  const int32_t* up = p.sched_host + S.upd_ptr;
-  double* rec = p.ws + L.rec;
   for (int it = 0; it < n_iters; ++it) {
-    k_pg_lin<true><<<nblk(p.n_edges, kPgWG), kPgWG, 0, s>>>(p, nullptr, 0, rec, kPgRec, rec + 6, rec + 42, kPgRec);
-    SLAM_LAUNCHED("k_pg_lin");
-    k_pg_zero<<<(int)a.n_tiles, kTlWG, 0, s>>>(a);
-    SLAM_LAUNCHED("k_pg_zero");
-    k_pg_assemble<<<p.n_poses + a.P, kPgWG, 0, s>>>(a);
-    SLAM_LAUNCHED("k_pg_assemble");
-    for (int k = 0; k < a.T; ++k) {
-      k_pg_panel<<<1 + cp[k + 1] - cp[k], kTlWG, 0, s>>>(a, k);
-      SLAM_LAUNCHED("k_pg_panel");
-      if (up[k + 1] > up[k]) {
-        k_pg_update<<<up[k + 1] - up[k], kTlWG, 0, s>>>(a, k);
-        SLAM_LAUNCHED("k_pg_update");
-      }
-    }
+    if (int rc = pg_launch_factor<false>(a, s)) return rc;
     for (int k = a.T - 1; k >= 0; --k) {
       k_pg_back<<<1, kTlWG, 0, s>>>(a, k);
       SLAM_LAUNCHED("k_pg_back");
@@ -874,5 +1365,49 @@ extern "C" int slam_pg_jacobian(const slam_pg_problem* prob, double* d_Ji, doubl
   k_pg_lin<true><<<nblk(prob->n_edges, kPgWG), kPgWG, 0, slam::as_stream(stream)>>>(
       *prob, nullptr, 0, nullptr, 0, d_Ji, d_Jj, 36);
   SLAM_LAUNCHED("k_pg_lin");
+  return SLAM_OK;
+}
+
+extern "C" long long slam_pg_cov_workspace_len(int n_poses, int n_cols) {
+  const int T = n_poses >= 1 && n_poses <= (1 << 24) ? (n_poses + kPgTP - 1) / kPgTP : 0;  // 0: refused below
+  if (n_cols < 1 || n_cols > T) {
+    slam::set_error("slam_pg_cov_workspace_len: bad sizes %d poses, %d tile columns", n_poses, n_cols);
+    return SLAM_ERR_ARG;
+  }
+  return PgCovLayout(T, n_cols).total;
+}
+
+extern "C" int slam_pg_covariance(const slam_pg_problem* prob, const int32_t* d_pairs, const int32_t* pairs_host,
+                                  int n_pairs, double rank_tol, double* d_cov, double* d_ws, long long ws_len,
+                                  int32_t* d_status, void* stream) {
+  PgArgs a;
+  PgCovGeom g;
+  if (int rc = pg_cov_check("slam_pg_covariance", prob, d_pairs, pairs_host, n_pairs, false, rank_tol, d_ws, ws_len,
+                            d_status, &a, &g))
+    return rc;
+  SLAM_REQUIRE(d_cov != nullptr, "slam_pg_covariance: null pointer");
+  hipStream_t s = slam::as_stream(stream);
+  if (int rc = pg_cov_launch(a, g, d_pairs, n_pairs, false, rank_tol, d_ws, d_status, s)) return rc;
+  k_pg_cov_pick<<<n_pairs, 64, 0, s>>>(a, d_pairs, d_ws, g.n_cols, d_cov);
+  SLAM_LAUNCHED("k_pg_cov_pick");
+  return SLAM_OK;
+}
+
+extern "C" int slam_pg_gate(const slam_pg_problem* prob, const int32_t* d_cand_ij, const int32_t* cand_ij_host,
+                            const double* d_meas, const double* d_sqrt_info, int n_cand, double rank_tol,
+                            double* d_d2, double* d_P, double* d_e, double* d_ws, long long ws_len,
+                            int32_t* d_status, void* stream) {
+  PgArgs a;
+  PgCovGeom g;
+  if (int rc = pg_cov_check("slam_pg_gate", prob, d_cand_ij, cand_ij_host, n_cand, true, rank_tol, d_ws, ws_len,
+                            d_status, &a, &g))
+    return rc;
+  SLAM_REQUIRE(d_meas != nullptr, "slam_pg_gate: null pointer");
+  SLAM_REQUIRE(d_d2 != nullptr || d_P != nullptr || d_e != nullptr, "slam_pg_gate: null outputs");
+  hipStream_t s = slam::as_stream(stream);
+  if (int rc = pg_cov_launch(a, g, d_cand_ij, n_cand, true, rank_tol, d_ws, d_status, s)) return rc;
+  k_pg_gate<<<nblk(n_cand, kPgWG), kPgWG, 0, s>>>(a, d_cand_ij, d_meas, d_sqrt_info, n_cand, d_ws, g.n_cols,
+                                                  rank_tol, d_d2, d_P, d_e, d_status);
+  SLAM_LAUNCHED("k_pg_gate");
   return SLAM_OK;
 }

@@ -148,6 +148,9 @@ SIGNATURES = {
     "slam_pg_iterate": [_PG, c_int, c_p],
     "slam_pg_residual": [_PG, c_p, c_p, c_p],
     "slam_pg_jacobian": [_PG, c_p, c_p, c_p],
+    "slam_pg_cov_workspace_len": [c_int, c_int],
+    "slam_pg_covariance": [_PG, c_p, c_p, c_int, c_double, c_p, c_p, c_longlong, c_p, c_p],
+    "slam_pg_gate": [_PG, c_p, c_p, c_p, c_p, c_int, c_double, c_p, c_p, c_p, c_p, c_longlong, c_p, c_p],
     "slam_fast_tiles_workspace_bytes": [c_int, c_int, c_int, c_int, c_int, c_int,
                                         ctypes.POINTER(c_size_t)],
     "slam_fast_tiles": [c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_p,
@@ -187,7 +190,8 @@ _RESTYPE = {"slam_last_error": ctypes.c_char_p, "slam_ba_sys_len": ctypes.c_long
             "slam_pnp_scratch_len": ctypes.c_longlong,
             "slam_fundamental_workspace_len": ctypes.c_longlong,
             "slam_pose_chain_workspace_len": ctypes.c_longlong,
-            "slam_pg_workspace_len": ctypes.c_longlong}
+            "slam_pg_workspace_len": ctypes.c_longlong,
+            "slam_pg_cov_workspace_len": ctypes.c_longlong}
 
 
 class SlamError(RuntimeError):

@@ -14,8 +14,10 @@ The drop-in names live in slam355.BundleAdjustment.
 The general SE(3) pose graph (csrc/posegraph_se3.hip) is beside
 it: weighted relative-pose edges between arbitrary keyframes, LM on the device
 over a skyline tile Cholesky:
-  PoseGraph                      the device-resident graph and its LM
+  PoseGraph                      the device-resident graph and its LM; covariance /
+                                 relative_covariance / gate
   pg_schedule                    the host-built schedule of the skyline factor
+  pg_cov_plan                    the tile columns a covariance request costs
   relative_pose                  the measurement an edge stores
   edges_from_ba                  weighted edges from a refined BA window
 """
@@ -275,6 +277,49 @@ def edges_from_ba(problem, pairs, scale="unit", rank_tol=1e-8):
     return np.ascontiguousarray(pr, np.int32), meas, info
 
 
+CHI2_6_99 = 16.811893829770927  # the 0.99 quantile of chi^2 with 6 degrees of freedom
+
+
+def _cov_list(n_poses, a, what, distinct=False):
+    """`a` as a contiguous non-empty int32 [m, 2] list of pose indices."""
+    a = np.asarray(a)
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"{what} must be integer pose indices")
+    if a.ndim != 2 or a.shape[1] != 2 or len(a) == 0:
+        raise ValueError(f"{what} must be a non-empty [m, 2] list, not shape {list(a.shape)}")
+    if int(n_poses) < 1 or a.min() < 0 or a.max() >= n_poses:
+        raise ValueError(f"{what}: index outside [0, {n_poses})")
+    if distinct and np.any(a[:, 0] == a[:, 1]):
+        raise ValueError(f"{what}: an entry joins a pose to itself")
+    return np.ascontiguousarray(a, np.int32)
+
+
+def pg_cov_plan(n_poses, pairs, gate=False):
+    """What a covariance request costs (slam_pg_covariance).
+    Block (a, b) is read from the tile column of the larger index: `requests`
+    [m, 2] holds (min, max) per entry, so a pair in either order is the same
+    request; `cols` the distinct tile columns max // PG_TILE_POSES, ascending,
+    each one 64-column solve through the factor; `low` the lowest tile row min
+    // PG_TILE_POSES asked of each column (the backward sweep of a column
+    stops there).  gate: the entries are candidate edges, which also need both
+    poses' own blocks.  Pure NumPy; len(cols) sizes the workspace."""
+    pr = _cov_list(n_poses, pairs, "pairs")
+    req = np.stack([pr.min(1), pr.max(1)], 1)
+    r, c = req[:, 0] // PG_TILE_POSES, req[:, 1] // PG_TILE_POSES
+    if gate:
+        r, c = np.concatenate([r, r]), np.concatenate([c, r])
+    cols = np.unique(c)
+    low = np.array([r[c == k].min() for k in cols], np.int32)
+    return dict(requests=req.astype(np.int32), cols=cols.astype(np.int32), low=low)
+
+
+def _rank_tol(rank_tol):
+    rank_tol = float(rank_tol)
+    if not (np.isfinite(rank_tol) and 0.0 <= rank_tol < 1.0):
+        raise ValueError(f"rank_tol must be finite and in [0, 1), not {rank_tol!r}")
+    return rank_tol
+
+
 class PoseGraph:
     """A device-resident SE(3) pose graph and its Levenberg-Marquardt.
 
@@ -401,3 +446,129 @@ class PoseGraph:
         Jj = torch.empty_like(Ji)
         _lib.call("slam_pg_jacobian", ctypes.byref(self._s), ptr(Ji), ptr(Jj), self._sp())
         return Ji.cpu().numpy(), Jj.cpu().numpy()
+
+    # ------------------------------------------------------------------ covariance
+    def _cov_ws(self, n_cols):
+        """The covariance workspace for n_cols tile columns (grown on demand and
+        kept) and the two status words."""
+        n = int(_lib.lib.slam_pg_cov_workspace_len(self.N, int(n_cols)))
+        if n < 0:
+            raise _lib.SlamError(_lib.lib.slam_last_error().decode())
+        dev = self.t["state"].device
+        if getattr(self, "_cws", None) is None or self._cws.numel() < n:
+            self._cws = None
+            self._cws = torch.empty(n, dtype=torch.float64, device=dev)
+        if getattr(self, "_cov_status", None) is None:
+            self._cov_status = torch.zeros(2, dtype=torch.int32, device=dev)
+        return self._cws
+
+    def cov_status(self) -> int:
+        """Status of the last covariance / gate call: 0 ok, 1 H0 not positive definite."""
+        return int(self._cov_status[0].item())
+
+    def gate_undetermined(self) -> int:
+        """Candidates of the last gate / relative_covariance call whose d2 is NaN
+        because their own S = P + R failed the rank test."""
+        return int(self._cov_status[1].item())
+
+    def _cov_raise(self, rank_tol):
+        if self.cov_status() != 0:
+            raise np.linalg.LinAlgError(
+                "pose-graph covariance: J~^T J~ is not positive definite at "
+                f"rank_tol {rank_tol:g} (fix the gauge: hold one pose whole)")
+
+    def covariance(self, poses=None, pairs=None, rank_tol=1e-8, device=False):
+        """Blocks of Sigma = (J~^T J~)^-1 at the live poses, zero damping, J~
+        the Jacobian of the LM steps (robust and information weights, held
+        columns out): [m, 6, 6] float64, Cov(x_a, x_a) per pose a of `poses`,
+        then Cov(x_a, x_b) per (a, b) of `pairs` (None, None: every pose's own
+        block), in the unit of the edges' information.  A pose's own block is
+        exactly symmetric, block (a, b) is block (b, a) transposed bit for bit,
+        rows and columns of held parameters are exactly 0.  The gauge is the
+        caller's (hold one pose): np.linalg.LinAlgError when a pivot of the
+        factor is not finite or L_rr^2 <= rank_tol H_rr.  device=True returns
+        the device tensor without that host check (NaN blocks then;
+        cov_status()).  Each distinct tile column max(a, b) // 10 costs one
+        64-column solve and T 64x64 tiles of workspace (pg_cov_plan): ask for
+        what is needed on a long trajectory.  Overwrites the LM workspace, not
+        the poses or the LM state; iterate() rebuilds it."""
+        out = []
+        if poses is None and pairs is None:
+            poses = np.arange(self.N)
+        if poses is not None:
+            c = np.asarray(poses)
+            if c.ndim != 1 or c.dtype == np.bool_ or not np.issubdtype(c.dtype, np.integer) or len(c) == 0:
+                raise ValueError("poses must be a non-empty list of integer pose indices")
+            out.append(_cov_list(self.N, np.stack([c, c], 1), "poses"))
+        if pairs is not None:
+            out.append(_cov_list(self.N, pairs, "pairs"))
+        pr = np.ascontiguousarray(np.concatenate(out), np.int32)
+        rank_tol = _rank_tol(rank_tol)
+        plan = pg_cov_plan(self.N, pr)
+        dev = self.t["state"].device
+        with torch.cuda.stream(self.stream if self.stream is not None else torch.cuda.current_stream()):
+            ws = self._cov_ws(len(plan["cols"]))
+            tp = torch.from_numpy(pr).to(dev)
+            cov = torch.empty((len(pr), 6, 6), dtype=torch.float64, device=dev)
+            _lib.call("slam_pg_covariance", ctypes.byref(self._s), ptr(tp), pr.ctypes.data, len(pr), rank_tol,
+                      ptr(cov), ptr(ws), ws.numel(), ptr(self._cov_status), self._sp())
+            if device:
+                return cov
+            host = cov.cpu().numpy()
+        self._cov_raise(rank_tol)
+        return host
+
+    def gate(self, edges, meas, information=None, sqrt_information=None, rank_tol=1e-8, chi2=CHI2_6_99):
+        """Is a proposed edge consistent with the graph?  For candidates k =
+        (i, j) of `edges` [m, 2] with measurements `meas` [m, 6] (z = T_i^-1
+        T_j, relative_pose) -- which need not be edges of the graph -- the raw
+        residual e [m, 6] at the live poses, its first-order covariance under
+        the graph P [m, 6, 6] (J_i S_ii J_i^T + J_i S_ij J_j^T + its transpose
+        + J_j S_jj J_j^T over the blocks of covariance()), and the squared
+        Mahalanobis distance d2 [m] = e^T (P + R)^-1 e with R the inverse of
+        the candidate's information (`information` [m, 6, 6], factored as in
+        the constructor, or `sqrt_information`; neither: R = 0).  accept =
+        d2 <= chi2 (default: the 0.99 quantile of chi^2 with 6 degrees of
+        freedom).  A candidate whose P + R fails rank_tol's rule (both poses
+        held and R = 0) has d2 = NaN and is not accepted (gate_undetermined()).
+        LinAlgError, cost and what is overwritten: as covariance()."""
+        cand = _cov_list(self.N, edges, "edges", distinct=True)
+        z = np.ascontiguousarray(np.asarray(meas, np.float64).reshape(-1, 6))
+        if len(z) != len(cand):
+            raise ValueError("meas must hold 6 values per candidate")
+        if information is not None and sqrt_information is not None:
+            raise ValueError("give information or sqrt_information, not both")
+        A = None
+        if information is not None:
+            info = np.asarray(information, np.float64).reshape(len(cand), 6, 6)
+            A = np.stack([np.linalg.cholesky(m).T for m in info])
+        elif sqrt_information is not None:
+            A = np.asarray(sqrt_information, np.float64).reshape(len(cand), 6, 6)
+        if not np.all(np.isfinite(z)) or (A is not None and not np.all(np.isfinite(A))):
+            raise ValueError("meas and the information must be finite")
+        chi2 = float(chi2)
+        if not chi2 > 0.0:
+            raise ValueError(f"chi2 must be positive, not {chi2!r}")
+        rank_tol = _rank_tol(rank_tol)
+        plan = pg_cov_plan(self.N, cand, gate=True)
+        dev = self.t["state"].device
+        T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+        m = len(cand)
+        with torch.cuda.stream(self.stream if self.stream is not None else torch.cuda.current_stream()):
+            ws = self._cov_ws(len(plan["cols"]))
+            tc, tz, tA = T(cand), T(z), (T(A) if A is not None else None)
+            d2 = torch.empty(m, dtype=torch.float64, device=dev)
+            P = torch.empty((m, 6, 6), dtype=torch.float64, device=dev)
+            e = torch.empty((m, 6), dtype=torch.float64, device=dev)
+            _lib.call("slam_pg_gate", ctypes.byref(self._s), ptr(tc), cand.ctypes.data, ptr(tz), ptr(tA), m,
+                      rank_tol, ptr(d2), ptr(P), ptr(e), ptr(ws), ws.numel(), ptr(self._cov_status), self._sp())
+            d2, P, e = d2.cpu().numpy(), P.cpu().numpy(), e.cpu().numpy()
+        self._cov_raise(rank_tol)
+        return dict(d2=d2, P=P, e=e, accept=d2 <= chi2)
+
+    def relative_covariance(self, pairs, rank_tol=1e-8):
+        """First-order covariance [m, 6, 6] of relative_pose(x_i, x_j) for the
+        (i, j) of `pairs`, i != j, under the graph: the gate's P with zero
+        measurements and no information."""
+        pr = _cov_list(self.N, pairs, "pairs", distinct=True)
+        return self.gate(pr, np.zeros((len(pr), 6)), rank_tol=rank_tol)["P"]
