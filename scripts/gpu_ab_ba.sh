@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-4 session-2 second pass: BA tiled-solve tests at the current library,
 # C4 and C5 A/B against a variant (default: the 2x2-pivot factor alone), and
-# the per-column flow-solve timeline (profiling build of the current ba.hip).
+# the per-column flow-solve timeline (profiling build of the current BA files).
 #   scripts/gpu_ab_ba.sh TAG VARIANT_SO
 set -o pipefail
 ROOT="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"

@@ -5,11 +5,14 @@
 // and scipy least_squares TRF) with LM on the normal equations, all state on
 // the device so a fixed number of iterations runs with no host round trip.
 //
-// One LM iteration = 4 launches (local BA); k_solve_blk is in
-// ba_solve.hip, every other kernel in this file.  Shared: ba_common.hpp (batch
-// descriptor, solver-side helpers, the host functions that cross the files),
-// ba_layout.hpp, ba_project.hpp (cam_prep), ba_epilogue.hpp (solve epilogue),
-// dpp_fmac.hpp (fused DPP broadcast FMAs).
+// One LM iteration = 4 launches (local BA).  This file holds the
+// linearisers with the fold, k_assemble, the point step and the decision, and
+// the LM entry points; the camera solve is in ba_solve.hip (k_solve_blk) and
+// ba_tiled.hip (k_tl3_flow / k_tl2_*), the covariance in ba_cov.hip.  Shared:
+// ba_common.hpp (batch descriptor, solver-side helpers, the host functions that
+// cross the files), ba_layout.hpp, ba_project.hpp (cam_prep and the
+// per-observation projection), ba_epilogue.hpp (solve epilogue), dpp_fmac.hpp
+// (fused DPP broadcast FMAs).
 //   k_linearize     point group -> residuals + Jacobians, V*_p, e_p = V*^-1 g_p,
 //                                  W_o = Jc^T Jp, u_o = Jp e_p, and the group's
 //                                  slot partials of the reduced camera system:
@@ -19,7 +22,7 @@
 //                             b = -Jc^T r - Jc^T u, g, diag U, cost
 //   (all-reduce of sys over ranks happens here for multi-GPU)
 //   k_solve_blk     1 WG   -> damp, blocked LDL^T (MFMA trailing updates), camera  [ba_solve.hip]
-//                             step, pred_cam, trial cameras (tiled k_tl3_flow / k_tl2_* for 9C > 120)
+//                             step, pred_cam, trial cameras (tiled k_tl3_flow / k_tl2_* for 9C > 120)  [ba_tiled.hip]
 //   k_back_trial    point group -> point step, trial points, trial |r|^2 and
 //                                  pred partials; the last group sums them into
 //                                  small (and, single rank, decides)
@@ -30,32 +33,14 @@
 #include "ba_layout.hpp"
 #include "ba_project.hpp"
 #include "dpp_fmac.hpp"
-#include "tile_f64.hpp"
 
 using slam::Launch;
+using slam::launch_build;
+using slam::make_launch;
 
 namespace {
 
-// Cross-workgroup hand-off inside one launch (ticket pattern): the partials
-// are stored and loaded with agent-scope relaxed atomics, i.e. write-through
-// `sc1` stores and `sc1` loads that bypass the per-XCD L2, so no L2-wide
-// release/acquire fence is needed (MI355X_MICROARCH.md, correctness table).
-__device__ __forceinline__ void st_sc1(double* p, double v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ double ld_sc1(const double* p) {
-  return __hip_atomic_load(const_cast<double*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ unsigned ticket_add(uint32_t* p) {
-  return __hip_atomic_fetch_add(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void ticket_reset(uint32_t* p) {
-  __hip_atomic_store(p, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-constexpr double kClamp = 5000.0;
 constexpr double kLamMin = 1e-16, kLamMax = 1e32;
-constexpr int kBS = 256;   // block size of the element-wise kernels
 
 // The batched per-observation / per-block launches (grid x = the problem's
 // workgroups, y = problem) with 8k problems: workgroups are dealt round-robin
@@ -79,264 +64,6 @@ __device__ __forceinline__ int2 ba_xcd_map() {
   const int2 bw_ = ba_xcd_map();     \
   const int bx = bw_.x;              \
   const slam_ba_problem& p = (b).p[bw_.y]
-// ---------------------------------------------------------------- projection
-// Residual (proj - q) of BundleAdjustment.py:317-337 with the operation order
-// of the numpy code, and optionally its analytic 2x12 Jacobian, from a camera
-// record of cam_prep.
-template <bool JAC>
-__device__ __forceinline__ void reproject_pre(const double* __restrict__ cr,
-                                              const double* __restrict__ X,
-                                              const double* __restrict__ q, double r[2],
-                                              double J[2][12]) {
-  const double c = cr[0], s = cr[1], omc = cr[2];
-  const double v0 = cr[3], v1 = cr[4], v2 = cr[5];
-  const double X0 = X[0], X1 = X[1], X2 = X[2];
-  const double dot = X0 * v0 + X1 * v1 + X2 * v2;
-  const double cx0 = v1 * X2 - v2 * X1;
-  const double cx1 = v2 * X0 - v0 * X2;
-  const double cx2 = v0 * X1 - v1 * X0;
-  const double dk = dot * omc;
-  const double RX0 = c * X0 + s * cx0 + dk * v0;
-  const double RX1 = c * X1 + s * cx1 + dk * v1;
-  const double RX2 = c * X2 + s * cx2 + dk * v2;
-  const double P0 = RX0 + cr[26], P1 = RX1 + cr[27], P2 = RX2 + cr[28];
-  const double p0 = -P0 / P2, p1 = -P1 / P2;
-  const double f = cr[29], k1 = cr[30], k2 = cr[31];
-  const double n = p0 * p0 + p1 * p1;
-  const double rad = 1.0 + k1 * n + k2 * (n * n);
-  const double sc = rad * f;
-  r[0] = p0 * sc - q[0];
-  r[1] = p1 * sc - q[1];
-  if constexpr (JAC) {
-    double R[3][3], A[3][3];
-    for (int i = 0; i < 9; ++i) {
-      R[i / 3][i % 3] = cr[6 + i];
-      A[i / 3][i % 3] = cr[15 + i];
-    }
-    double dR[3][3];
-    if (cr[25] != 0.0) {  // |w|^2 < 1e-24: -[RX]x
-      dR[0][0] = 0.0;  dR[0][1] = RX2;  dR[0][2] = -RX1;
-      dR[1][0] = -RX2; dR[1][1] = 0.0;  dR[1][2] = RX0;
-      dR[2][0] = RX1;  dR[2][1] = -RX0; dR[2][2] = 0.0;
-    } else {
-      const double Xs[3][3] = {{0.0, -X2, X1}, {X2, 0.0, -X0}, {-X1, X0, 0.0}};
-      double B[3][3];
-      for (int i = 0; i < 3; ++i)
-        for (int k = 0; k < 3; ++k)
-          B[i][k] = Xs[i][0] * A[0][k] + Xs[i][1] * A[1][k] + Xs[i][2] * A[2][k];
-      const double inv = cr[24];
-      for (int i = 0; i < 3; ++i)
-        for (int k = 0; k < 3; ++k)
-          dR[i][k] = (R[i][0] * B[0][k] + R[i][1] * B[1][k] + R[i][2] * B[2][k]) * inv;
-    }
-    // dp/dP
-    const double iz = 1.0 / P2;
-    const double dpP[2][3] = {{-iz, 0.0, P0 * iz * iz}, {0.0, -iz, P1 * iz * iz}};
-    // dproj/dp = sc I + 2 f (k1 + 2 k2 n) p p^T
-    const double g2 = 2.0 * f * (k1 + 2.0 * k2 * n);
-    const double Dp[2][2] = {{sc + g2 * p0 * p0, g2 * p0 * p1}, {g2 * p1 * p0, sc + g2 * p1 * p1}};
-    double D[2][3];
-    for (int a = 0; a < 2; ++a)
-      for (int k = 0; k < 3; ++k) D[a][k] = Dp[a][0] * dpP[0][k] + Dp[a][1] * dpP[1][k];
-    const double pp[2] = {p0, p1};
-    for (int a = 0; a < 2; ++a) {
-      for (int k = 0; k < 3; ++k) {
-        J[a][k] = D[a][0] * dR[0][k] + D[a][1] * dR[1][k] + D[a][2] * dR[2][k];
-        J[a][3 + k] = D[a][k];
-        J[a][9 + k] = D[a][0] * R[0][k] + D[a][1] * R[1][k] + D[a][2] * R[2][k];
-      }
-      J[a][6] = pp[a] * rad;
-      J[a][7] = pp[a] * (f * n);
-      J[a][8] = pp[a] * (f * n * n);
-    }
-  }
-}
-
-// Single-call form (standalone residual / Jacobian entry points).
-template <bool JAC>
-__device__ __forceinline__ void reproject(const double* __restrict__ cam,
-                                          const double* __restrict__ X,
-                                          const double* __restrict__ q, double r[2],
-                                          double J[2][12]) {
-  double cr[kCamRec];
-  cam_prep(cam, cr);
-  reproject_pre<JAC>(cr, X, q, r, J);
-}
-
-// The two clamps of BundleAdjustment.py:339-350 (x first, then y on the
-// rescaled row), with the chain rule applied to J when JAC.
-template <bool JAC>
-__device__ __forceinline__ void clamp_rows(double r[2], double J[2][12]) {
-#pragma unroll
-  for (int comp = 0; comp < 2; ++comp) {
-    const double rc = r[comp];
-    if (fabs(rc) > kClamp) {
-      const double arc = fabs(rc);
-      const double half = comp == 0 ? 613.0 : 185.0;
-      if constexpr (JAC) {
-        const double a = (half * 2.0) / arc;
-        double Jc[12];
-        for (int k = 0; k < 12; ++k) Jc[k] = J[comp][k];
-        for (int row = 0; row < 2; ++row) {
-          const double ratio = r[row] / rc;
-          for (int k = 0; k < 12; ++k) J[row][k] = a * (J[row][k] - ratio * Jc[k]);
-        }
-      }
-      r[0] = r[0] / arc * half * 2.0;
-      r[1] = r[1] / arc * half * 2.0;
-    }
-  }
-}
-
-// Held camera parameters (slam_ba_problem.cam_fixed): bit i of a camera's mask
-// word removes column i of the 2 x 9 camera block of its observations, before
-// the block enters any product, so the row and column of that parameter in the
-// reduced camera system are zero up to the damped diagonal and its step is an
-// exact zero.  (After the clamp: its chain rule is per column, 0 stays 0.)
-__device__ __forceinline__ void hold_cols(double J[2][12], unsigned fx) {
-#pragma unroll
-  for (int i = 0; i < 9; ++i)
-    if ((fx >> i) & 1u) J[0][i] = J[1][i] = 0.0;
-}
-// the two-lane form: half H holds camera columns 6 H .. 6 H + 5 (H = 1: 6..8)
-template <int H>
-__device__ __forceinline__ void hold_cols_half(double Jh[2][6], unsigned fx) {
-#pragma unroll
-  for (int i = 0; i < (H == 0 ? 6 : 3); ++i)
-    if ((fx >> (6 * H + i)) & 1u) Jh[0][i] = Jh[1][i] = 0.0;
-}
-
-// Robust loss per observation (slam_ba_problem.loss != 0, delta = loss_scale):
-// with s = |r|^2 of the clamped residual and z = s / delta^2, r and the lane's
-// NC Jacobian columns (J0, J1: rows 0, 1; 12, a half's 6, or 0 = none) are
-// scaled by sqrt(w), w = rho'(z), and delta^2 rho(z) is returned -- the
-// observation's term of twice the LM cost, in place of s.  Both lanes of a
-// split observation hold the full r, so both form the same w.  After the clamp
-// and hold_cols (a held column is 0 and stays 0).  huber with z <= 1 is the
-// plain loss exactly: nothing is scaled, s is returned.
-template <int NC>
-__device__ __forceinline__ double robust_weight(double r[2], double* J0, double* J1, int loss,
-                                                double delta) {
-  const double s = r[0] * r[0] + r[1] * r[1];
-  const double d2 = delta * delta;
-  const double z = s / d2;
-  double sw, rho;
-  if (loss == 1) {         // huber: rho = z | 2 sqrt(z) - 1, w = 1 | 1 / sqrt(z)
-    if (z <= 1.0) return s;
-    const double q = sqrt(z);
-    sw = 1.0 / sqrt(q);
-    rho = 2.0 * q - 1.0;
-  } else if (loss == 2) {  // soft_l1: rho = 2 (sqrt(1 + z) - 1), w = 1 / sqrt(1 + z)
-    const double q = sqrt(1.0 + z);
-    sw = 1.0 / sqrt(q);
-    rho = 2.0 * z / (q + 1.0);  // = 2 (q - 1) without the cancellation at small z
-  } else {                 // cauchy: rho = log(1 + z), w = 1 / (1 + z)
-    sw = 1.0 / sqrt(1.0 + z);
-    rho = log1p(z);
-  }
-  r[0] *= sw;
-  r[1] *= sw;
-#pragma unroll
-  for (int k = 0; k < NC; ++k) {
-    J0[k] *= sw;
-    J1[k] *= sw;
-  }
-  return d2 * rho;
-}
-
-// reproject_pre<true> + clamp_rows<true> split over two lanes by Jacobian
-// columns: H = 0 the rotation / translation columns 0..5, H = 1 the f, k1, k2
-// and point columns 6..11 (Jh[a][k] = J[a][6 H + k]).  Both halves run the
-// forward projection; every value is computed with the same operations in
-// the same order as the one-lane form (the clamp's chain rule is per column).
-template <int H>
-__device__ __forceinline__ void reproject_half(const double* __restrict__ cr,
-                                               const double* __restrict__ X,
-                                               const double* __restrict__ q, double r[2],
-                                               double Jh[2][6]) {
-  const double c = cr[0], s = cr[1], omc = cr[2];
-  const double v0 = cr[3], v1 = cr[4], v2 = cr[5];
-  const double X0 = X[0], X1 = X[1], X2 = X[2];
-  const double dot = X0 * v0 + X1 * v1 + X2 * v2;
-  const double cx0 = v1 * X2 - v2 * X1;
-  const double cx1 = v2 * X0 - v0 * X2;
-  const double cx2 = v0 * X1 - v1 * X0;
-  const double dk = dot * omc;
-  const double RX0 = c * X0 + s * cx0 + dk * v0;
-  const double RX1 = c * X1 + s * cx1 + dk * v1;
-  const double RX2 = c * X2 + s * cx2 + dk * v2;
-  const double P0 = RX0 + cr[26], P1 = RX1 + cr[27], P2 = RX2 + cr[28];
-  const double p0 = -P0 / P2, p1 = -P1 / P2;
-  const double f = cr[29], k1 = cr[30], k2 = cr[31];
-  const double n = p0 * p0 + p1 * p1;
-  const double rad = 1.0 + k1 * n + k2 * (n * n);
-  const double sc = rad * f;
-  r[0] = p0 * sc - q[0];
-  r[1] = p1 * sc - q[1];
-  const double iz = 1.0 / P2;
-  const double dpP[2][3] = {{-iz, 0.0, P0 * iz * iz}, {0.0, -iz, P1 * iz * iz}};
-  const double g2 = 2.0 * f * (k1 + 2.0 * k2 * n);
-  const double Dp[2][2] = {{sc + g2 * p0 * p0, g2 * p0 * p1}, {g2 * p1 * p0, sc + g2 * p1 * p1}};
-  double D[2][3];
-  for (int a = 0; a < 2; ++a)
-    for (int k = 0; k < 3; ++k) D[a][k] = Dp[a][0] * dpP[0][k] + Dp[a][1] * dpP[1][k];
-  if constexpr (H == 0) {
-    double dR[3][3];
-    if (cr[25] != 0.0) {
-      dR[0][0] = 0.0;  dR[0][1] = RX2;  dR[0][2] = -RX1;
-      dR[1][0] = -RX2; dR[1][1] = 0.0;  dR[1][2] = RX0;
-      dR[2][0] = RX1;  dR[2][1] = -RX0; dR[2][2] = 0.0;
-    } else {
-      double R[3][3], A[3][3];
-      for (int i = 0; i < 9; ++i) {
-        R[i / 3][i % 3] = cr[6 + i];
-        A[i / 3][i % 3] = cr[15 + i];
-      }
-      const double Xs[3][3] = {{0.0, -X2, X1}, {X2, 0.0, -X0}, {-X1, X0, 0.0}};
-      double B[3][3];
-      for (int i = 0; i < 3; ++i)
-        for (int k = 0; k < 3; ++k)
-          B[i][k] = Xs[i][0] * A[0][k] + Xs[i][1] * A[1][k] + Xs[i][2] * A[2][k];
-      const double inv = cr[24];
-      for (int i = 0; i < 3; ++i)
-        for (int k = 0; k < 3; ++k)
-          dR[i][k] = (R[i][0] * B[0][k] + R[i][1] * B[1][k] + R[i][2] * B[2][k]) * inv;
-    }
-    for (int a = 0; a < 2; ++a)
-      for (int k = 0; k < 3; ++k) {
-        Jh[a][k] = D[a][0] * dR[0][k] + D[a][1] * dR[1][k] + D[a][2] * dR[2][k];
-        Jh[a][3 + k] = D[a][k];
-      }
-  } else {
-    double R[3][3];
-    for (int i = 0; i < 9; ++i) R[i / 3][i % 3] = cr[6 + i];
-    const double pp[2] = {p0, p1};
-    for (int a = 0; a < 2; ++a) {
-      Jh[a][0] = pp[a] * rad;
-      Jh[a][1] = pp[a] * (f * n);
-      Jh[a][2] = pp[a] * (f * n * n);
-      for (int k = 0; k < 3; ++k) Jh[a][3 + k] = D[a][0] * R[0][k] + D[a][1] * R[1][k] + D[a][2] * R[2][k];
-    }
-  }
-#pragma unroll
-  for (int comp = 0; comp < 2; ++comp) {  // clamp_rows<true> on this lane's columns
-    const double rc = r[comp];
-    if (fabs(rc) > kClamp) {
-      const double arc = fabs(rc);
-      const double half = comp == 0 ? 613.0 : 185.0;
-      const double a = (half * 2.0) / arc;
-      double Jc[6];
-      for (int k = 0; k < 6; ++k) Jc[k] = Jh[comp][k];
-      for (int row = 0; row < 2; ++row) {
-        const double ratio = r[row] / rc;
-        for (int k = 0; k < 6; ++k) Jh[row][k] = a * (Jh[row][k] - ratio * Jc[k]);
-      }
-      r[0] = r[0] / arc * half * 2.0;
-      r[1] = r[1] / arc * half * 2.0;
-    }
-  }
-}
-
 // ---------------------------------------------------------------- standalone
 __global__ __launch_bounds__(kBS) void k_residual(const double* __restrict__ cams,
                                                   const double* __restrict__ pts,
@@ -1519,1288 +1246,6 @@ __global__ __launch_bounds__(kAsmWG) void k_assemble(BaBatch bat) {
   if (diag && t == 0) costc[c1] = sh[108];
 }
 
-// ---------------------------------------------------------------- tiled solve
-// Large reduced camera systems (9C > kLdsMaxN: the sharded C4 window, global
-// BA): blocked Cholesky LL^T over 64x64 f64 tiles in the nested-dissection
-// tile order of ba.tl_schedule (symbolic structure on the host), two forms:
-//   k_tl3_flow    one launch, one persistent workgroup per tile column; device
-//                 flags replace launch boundaries (the default);
-//   k_tl2_*       the same tile operations level by level as separate launches
-//                 (when the columns cannot all be resident: more tiles than
-//                 the stream's CUs, or tl_mode "levels").
-// Both start from k_tl2_load / k_tl2_scatter (damped S -> lower tiles, b) and
-// end in solve_epilogue.  The diagonal-tile factor + inverse is
-// tile_chol_inv_blk (16x16 diagonal blocks in wave 0's registers, the rest on
-// the f64 matrix cores); it and the fragment / tile-product helpers live in
-// tile_f64.hpp, shared with the pose graph's skyline factor.
-constexpr int kTlHdr = 12;     // ints of the tile schedule's header
-constexpr int kEpiCams = 16;   // cameras per tile in k_tl3_flow's spread epilogue (ba.EPI_CAMS_MAX)
-
-struct TlLayout {  // doubles inside p.chol; T = the schedule's tile count (ba.tl_schedule)
-  int T, N;
-  long long a, dinv, b, y, x, nz, fail, xo, fc, epi, flow, total;
-  __host__ __device__ TlLayout(int n, int n_tiles) {
-    T = n_tiles;
-    N = T * kTB;
-    a = 0;
-    dinv = a + (long long)N * N;         // T tiles L_kk^-1 (row-major 64x64 each)
-    b = dinv + (long long)N * kTB;
-    y = b + N;
-    x = y + N;
-    nz = x + N;                          // T*T bytes
-    fail = nz + ((long long)T * T + 7) / 8;
-    xo = fail + 8;                       // fail flag + 7 spare slots (ba.py mirrors this layout)
-    fc = xo + N;                         // k_tl3_flow: x in camera order; [T][T][64] L_Ik y_k
-    epi = fc + (long long)T * T * kTB;   // (forward-substitution terms); [T][2] epilogue partials
-    flow = epi + 2 * T;                  // (pc, cost per tile), then ints: flags
-    // tile[T][T], y[T], x[T]; ticket, epoch, start ticket (+5 spare); retired row
-    // tiles + waiter mark cnt[T]; L_JJ^-1 / y_J published dv[T]
-    total = flow + ((long long)T * T + 4 * T + 8 + 1) / 2;
-    // then k_tl3_flow's product slots (tl_sched[11] of them, slam_ba_chol_len):
-    // [slots][64][64] terms L_Ik L_Jk^T, then one epoch flag (int) per slot
-  }
-  __host__ __device__ long long prod(int slot) const { return total + (long long)slot * kTB * kTB; }
-  __host__ __device__ long long with_slots(int n_slots) const {
-    return prod(n_slots) + ((long long)n_slots + 1) / 2;
-  }
-};
-
-// Fragment order with the offset inside each 64-double fragment F rotated by
-// (4 * (c & 3) + (F & 3)) mod 16 within its 16-row quarter: the MFMA result
-// layout (lanes along a row) then stores without LDS bank conflicts (16-way in
-// plain fragment order: a 16-lane group's doubles all sit 32 dwords apart),
-// and a fragment still reads back conflict-free (a permutation of each quarter).
-__device__ __forceinline__ int frag_swz(int r, int c) {
-  const int F = ((r >> 4) << 4) + (c >> 2), hi = c & 3;
-  return (F << 6) + (hi << 4) + (((r & 15) + 4 * hi + (F & 3)) & 15);
-}
-// gemm_xyT_lowY with both operands in frag_swz order (same products, same order)
-__device__ __forceinline__ void gemm_xyT_lowY_swz(const double* Xf, const double* Yf, d4 acc[4]) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int so[4];
-#pragma unroll
-  for (int k3 = 0; k3 < 4; ++k3) so[k3] = ((lane >> 4) << 4) + (((lane & 15) + 4 * (lane >> 4) + k3) & 15);
-#pragma unroll
-  for (int s = 0; s < 4; ++s) acc[s] = d4{0.0, 0.0, 0.0, 0.0};
-  static_for<0, 16>([&](auto K) {
-    constexpr int kk = decltype(K)::value;
-    const double a = Xf[((w * 16 + kk) << 6) + so[kk & 3]];
-    static_for<kk / 4, 4>([&](auto S) {
-      constexpr int s = decltype(S)::value;
-      acc[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Yf[((s * 16 + kk) << 6) + so[kk & 3]], acc[s], 0, 0, 0);
-    });
-  });
-}
-
-__device__ __forceinline__ bool tl_failed(const slam_ba_problem& p, const TlLayout& L) {
-  return *reinterpret_cast<const volatile int*>(p.chol + L.fail) != 0;
-}
-
-constexpr int kVR = 65;   // row stride of k_tl3_flow's row-major L_JJ^-1
-
-// ---------------------------------------------------------------- level-scheduled tiled solve
-// The same tile factor with the columns grouped by elimination-tree level
-// (slam355/ba.py tl_schedule: tiles renumbered by nested dissection of the
-// tile graph, symbolic structure on the host).  Per level: k_tl2_panel (WG per
-// (k, I) of every column k of the level: the diagonal WG stores L_kk^-1 and
-// y_k = L_kk^-1 b_k, the others L_Ik = A_Ik L_kk^-T), then k_tl2_update (WG
-// per target tile (I, J) of the level: A_IJ -= sum_k L_Ik L_Jk^T on the f64
-// matrix cores, and for I = J also b_I -= sum_k L_Ik y_k -- the sums over the
-// level's columns inside one WG, no atomics).  k_tl2_back walks the levels in
-// reverse: x_k = L_kk^-T (y_k - sum_I L_Ik^T x_I) over the ancestors I; then
-// k_tl2_unperm moves x back to the camera order (into the y region, which the
-// epilogue reads).  A banded window of T tiles runs ~log2 T levels instead of
-// T panel steps (C4: 4 levels for 9 tiles; C5: 8 for 71).
-// The schedule's row maps sit at fixed offsets after its kTlHdr-int header (ba.tl_schedule;
-// checked on the host in tl_check_sched), so no lookup waits on a header load:
-// row r of S (camera order) -> its row in the tiled system
-__device__ __forceinline__ int tl_new_row(const int32_t* sched, int r) { return sched[kTlHdr + r]; }
-// row of the tiled system -> row of S, -1 on a tile's padding rows
-__device__ __forceinline__ int tl_old_row(const int32_t* sched, int n, int rn) { return sched[kTlHdr + n + rn]; }
-// rows of S in tile k (they come first, padding after them)
-__device__ __forceinline__ const int32_t* tl_tile_rows(const int32_t* sched, int n, int T) {
-  return sched + kTlHdr + n + T * kTB;
-}
-
-// Zero the lower tiles (identity on the padded rows' diagonal), b in the new order.
-// struct_only: only the tiles the symbolic factor touches -- (J, J) and (I, J)
-// for the rows I of column J (column table; grid T x (1 + max rows)); every
-// other lower tile is never read by either solve form (C5: 71 diagonal + row
-// tiles of 2556 lower tiles).  Otherwise all T (T + 1) / 2 lower tiles.
-__global__ __launch_bounds__(kTlWG) void k_tl2_load(slam_ba_problem p, int T_, int struct_only) {
-  lm_wave_priority();
-  const int n = 9 * p.n_cams;
-  const TlLayout L(n, T_);
-  const int32_t* S = p.tl_sched;
-  int I, J;
-  bool first;
-  if (struct_only) {
-    J = blockIdx.x;
-    const int q = blockIdx.y;
-    const int32_t* rec = S + S[5] + 5 * J;
-    if (q > rec[1]) return;  // uniform; (0, 0) always runs
-    I = q == 0 ? J : S[rec[0] + q - 1];
-    first = blockIdx.x == 0 && q == 0;
-  } else {
-    const int idx = blockIdx.x;
-    I = (int)((sqrtf(8.0f * (float)idx + 1.0f) - 1.0f) * 0.5f);
-    while ((I + 1) * (I + 2) / 2 <= idx) ++I;
-    while (I * (I + 1) / 2 > idx) --I;
-    J = idx - I * (I + 1) / 2;
-    first = idx == 0;
-  }
-  double* A = p.chol + L.a;
-  for (int e = threadIdx.x; e < kTB * kTB; e += kTlWG) {
-    const int i = I * kTB + (e >> 6), j = J * kTB + (e & 63);
-    A[(size_t)i * L.N + j] = (i == j && tl_old_row(S, n, i) < 0) ? 1.0 : 0.0;  // identity on padding
-  }
-  if (I == J && threadIdx.x < kTB) {
-    const int r = tl_old_row(S, n, I * kTB + threadIdx.x);  // row of S landing at new row I*64 + t
-    p.chol[L.b + I * kTB + threadIdx.x] = r >= 0 ? p.sys[sys_vec_off(p.n_cams, p.n_blocks) + r] : 0.0;
-  }
-  if (first) {
-    // k_tl3_flow: a new solve epoch (its flags compare against it); the retire
-    // ticket, the start ticket and the per-column parent counters re-armed
-    int* fl = reinterpret_cast<int*>(p.chol + L.flow) + L.T * L.T + 2 * L.T;
-    for (int i = threadIdx.x; i < L.T; i += blockDim.x) fl[8 + i] = 0;
-    if (threadIdx.x == 0) {
-      *reinterpret_cast<int*>(p.chol + L.fail) = 0;
-      fl[0] = 0;
-      fl[1] = fl[1] + 1;
-      fl[2] = 0;
-    }
-  }
-}
-
-// One WG per packed block: its values at their renumbered positions (lower
-// tiles, full symmetric inside diagonal tiles), camera damping on the diagonal.
-__global__ __launch_bounds__(128) void k_tl2_scatter(slam_ba_problem p, int T_) {
-  lm_wave_priority();
-  const int n = 9 * p.n_cams;
-  const TlLayout L(n, T_);
-  const int32_t* S = p.tl_sched;
-  const int blk = blockIdx.x, t = threadIdx.x;
-  if (t >= 81) return;
-  const int c1 = p.blocks[2 * blk], c2 = p.blocks[2 * blk + 1];
-  const double* vec = p.sys + sys_vec_off(p.n_cams, p.n_blocks);
-  const int i = t / 9, j = t - 9 * (t / 9);
-  const int r = 9 * c1 + i, c = 9 * c2 + j;  // element (r, c) of S
-  double v = p.sys[(size_t)blk * 81 + t];
-  if (r == c) v += p.state[SLAM_BA_ST_LAMBDA] * clampd(vec[2 * n + r]);
-  double* A = p.chol + L.a;
-  const int rn = tl_new_row(S, r), cn = tl_new_row(S, c);
-  const int tr = rn / kTB, tc = cn / kTB;
-  if (tr >= tc) A[(size_t)rn * L.N + cn] = v;
-  if (c1 != c2 && tc >= tr) A[(size_t)cn * L.N + rn] = v;
-}
-
-__global__ __launch_bounds__(kTlWG) __attribute__((amdgpu_waves_per_eu(1, 1)))
-void k_tl2_panel(slam_ba_problem p, int T_, int eoff) {
-  lm_wave_priority();
-  const TlLayout L(9 * p.n_cams, T_);
-  if (tl_failed(p, L)) return;
-  const int32_t* S = p.tl_sched;
-  const int k = S[eoff + 2 * blockIdx.x], I = S[eoff + 2 * blockIdx.x + 1];
-  __shared__ double VX[2 * kTB * kTB];
-  double* Vf = VX;                        // L_kk^-1, fragment order
-  __shared__ double Xf[kTB * kTB];        // A_Ik, fragment order
-  __shared__ int okf;
-  double* A = p.chol + L.a;
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const double* Akk = A + (size_t)k * kTB * L.N + k * kTB;
-  double* AIk = A + (size_t)I * kTB * L.N + k * kTB;
-  if (I > k && w >= 2) tile_to_frag(AIk, L.N, Xf, w - 2, 2);
-  double x[kTB];
-  double* Mb = VX;
-  double* Xb = VX + kTB * kMS;
-  double* Tb = Xb + 10 * 16 * kBS17;
-  const bool ok = tile_chol_inv_blk(Akk, L.N, Mb, Xb, Tb, &okf, (tl_tile_rows(S, 9 * p.n_cams, T_)[k] + 15) >> 4);
-  if (w == 1) {
-    const int cb16 = lane >> 4;
-#pragma unroll
-    for (int m = 0; m < kTB; ++m)
-      x[m] = (m >> 4) >= cb16 ? Xb[blk_id(m >> 4, cb16) * 16 * kBS17 + (m & 15) * kBS17 + (lane & 15)]
-                              : 0.0;
-  }
-  __syncthreads();  // VX is reused below
-  if (w == 1) {
-    if (I == k) {
-      const double bc = p.chol[L.b + k * kTB + lane];
-      double* Vkk = p.chol + L.dinv + (size_t)k * kTB * kTB;
-#pragma unroll
-      for (int m = 0; m < kTB; ++m) Vkk[m * kTB + lane] = x[m];
-#pragma unroll
-      for (int m = 0; m < kTB; ++m) Vf[m * kTB + lane] = x[m] * bc;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      double y = 0.0;
-      for (int c = 0; c < kTB; ++c) y += Vf[lane * kTB + ((c + lane) & 63)];
-      p.chol[L.y + k * kTB + lane] = y;
-      if (!ok && lane == 0) *reinterpret_cast<int*>(p.chol + L.fail) = 1;
-    } else {
-#pragma unroll
-      for (int m = 0; m < kTB; ++m) Vf[frag_idx(m, lane)] = x[m];
-    }
-  }
-  if (I == k || !ok) return;
-  __syncthreads();
-  d4 acc[4];
-  gemm_xyT_lowY(Xf, Vf, acc);  // L_Ik = A_Ik (L_kk^-1)^T
-#pragma unroll
-  for (int s2 = 0; s2 < 4; ++s2)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = w * 16 + (lane >> 4) + 4 * r, col = s2 * 16 + (lane & 15);
-      AIk[(size_t)row * L.N + col] = acc[s2][r];
-    }
-}
-
-__global__ __launch_bounds__(kTlWG) void k_tl2_update(slam_ba_problem p, int T_, int eoff) {
-  lm_wave_priority();
-  const TlLayout L(9 * p.n_cams, T_);
-  if (tl_failed(p, L)) return;
-  const int32_t* S = p.tl_sched;
-  const int32_t* e = S + eoff + 4 * blockIdx.x;
-  const int I = e[0], J = e[1], ko = e[2], kc = e[3];
-  __shared__ double Xf[kTB * kTB], Yf[kTB * kTB];
-  __shared__ double part[4][kTB];
-  double* A = p.chol + L.a;
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  d4 acc[4];
-#pragma unroll
-  for (int s2 = 0; s2 < 4; ++s2) acc[s2] = d4{0.0, 0.0, 0.0, 0.0};
-  double bs = 0.0;  // thread (w, lane): sum over k of row lane's part [16w, 16w + 16) of L_Ik y_k
-  for (int q = 0; q < kc; ++q) {
-    const int k = S[ko + q];
-    const double* LIk = A + (size_t)I * kTB * L.N + k * kTB;
-    tile_to_frag(LIk, L.N, Xf);
-    if (I != J) tile_to_frag(A + (size_t)J * kTB * L.N + k * kTB, L.N, Yf);
-    if (I == J) {
-      const double* yk = p.chol + L.y + k * kTB;
-      for (int m = 16 * w; m < 16 * w + 16; ++m)
-        bs = __builtin_fma(LIk[(size_t)lane * L.N + m], yk[m], bs);
-    }
-    __syncthreads();
-    const double* Y = I == J ? Xf : Yf;
-#pragma unroll 4
-    for (int kk = 0; kk < 16; ++kk) {
-      const double a = Xf[((w * 16 + kk) << 6) + lane];
-#pragma unroll
-      for (int s2 = 0; s2 < 4; ++s2)
-        acc[s2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Y[((s2 * 16 + kk) << 6) + lane], acc[s2],
-                                                       0, 0, 0);
-    }
-    __syncthreads();  // Xf / Yf reloaded next k
-  }
-  double* AIJ = A + (size_t)I * kTB * L.N + J * kTB;
-#pragma unroll
-  for (int s2 = 0; s2 < 4; ++s2)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = w * 16 + (lane >> 4) + 4 * r, col = s2 * 16 + (lane & 15);
-      AIJ[(size_t)row * L.N + col] -= acc[s2][r];
-    }
-  if (I == J) {
-    part[w][lane] = bs;
-    __syncthreads();
-    if (t < kTB)
-      p.chol[L.b + I * kTB + t] -= ((part[0][t] + part[1][t]) + part[2][t]) + part[3][t];
-  }
-}
-
-// x_k = L_kk^-T (y_k - sum_I L_Ik^T x_I), I over the column's structure (ancestors).
-__global__ __launch_bounds__(kTlWG) void k_tl2_back(slam_ba_problem p, int T_, int eoff) {
-  lm_wave_priority();
-  const TlLayout L(9 * p.n_cams, T_);
-  if (tl_failed(p, L)) return;
-  const int32_t* S = p.tl_sched;
-  const int32_t* e = S + eoff + 3 * blockIdx.x;
-  const int k = e[0], so = e[1], sc = e[2];
-  __shared__ double r[kTB];
-  __shared__ double part[4][kTB];
-  const double* A = p.chol + L.a;
-  const int t = threadIdx.x, c = t & 63, q = t >> 6;
-  // thread (q, c): rows m in [16q, 16q + 16) of every L_Ik^T x_I, column c
-  double s2 = 0.0;
-  for (int u = 0; u < sc; ++u) {
-    const int I = S[so + u];
-    const double* LIk = A + (size_t)I * kTB * L.N + k * kTB;
-    const double* xI = p.chol + L.x + I * kTB;
-    for (int m = 16 * q; m < 16 * q + 16; ++m) s2 = __builtin_fma(LIk[(size_t)m * L.N + c], xI[m], s2);
-  }
-  part[q][c] = s2;
-  __syncthreads();
-  if (t < kTB) r[t] = p.chol[L.y + k * kTB + t] - (((part[0][t] + part[1][t]) + part[2][t]) + part[3][t]);
-  __syncthreads();
-  const double* Vkk = p.chol + L.dinv + (size_t)k * kTB * kTB;  // L_kk^-1
-  double s3 = 0.0;
-  for (int m = 16 * q; m < 16 * q + 16; ++m) s3 = __builtin_fma(Vkk[m * kTB + c], r[m], s3);
-  part[q][c] = s3;
-  __syncthreads();
-  if (t < kTB) p.chol[L.x + k * kTB + t] = ((part[0][t] + part[1][t]) + part[2][t]) + part[3][t];
-}
-
-// x (new tile order, L.x) -> camera order in the y region (read by the epilogue)
-__global__ __launch_bounds__(kTB) void k_tl2_unperm(slam_ba_problem p, int T_) {
-  const TlLayout L(9 * p.n_cams, T_);
-  const int I = blockIdx.x;  // new tile
-  const int r = tl_old_row(p.tl_sched, 9 * p.n_cams, I * kTB + threadIdx.x);
-  if (r >= 0) p.chol[L.y + r] = p.chol[L.x + I * kTB + threadIdx.x];
-}
-
-__global__ __launch_bounds__(1024) void k_tl2_epilogue(slam_ba_problem p, int T_) {
-  lm_wave_priority();
-  __shared__ double red[32];
-  const int n = 9 * p.n_cams;
-  const TlLayout L(n, T_);
-  const bool ok = !tl_failed(p, L);
-  const double* bvec = p.sys + sys_vec_off(p.n_cams, p.n_blocks);
-  const double* gvec = bvec + n;
-  solve_epilogue<true>(p, p.chol + L.y, ok, red,
-                       EpiSrc{gvec, bvec + 2 * n, p.cams[cur_of(p.state)], gvec + 2 * n});
-}
-
-// ---------------------------------------------------------------- dataflow tiled solve
-// The same factor as a dataflow graph in ONE launch: workgroup J owns tile
-// column J (new numbering) for the whole solve and, from the schedule's column
-// table (slam355/ba.py tl_schedule),
-//   (1) A_JJ -= sum_{k in rs(J)} L_Jk L_Jk^T  (waits for each L_Jk's flag),
-//       factor + inverse of the diagonal tile (tile_chol_inv_blk, from LDS);
-//   (2) per row tile I in rows(J), parent first: A_IJ -= sum_k L_Ik L_Jk^T,
-//       L_IJ = A_IJ L_JJ^-T, published (tile flag);
-//   (3) y_J = L_JJ^-1 (b_J - sum_{k in rs(J)} L_Jk y_k)  (waits for y_k);
-//   (4) x_J = L_JJ^-T (y_J - sum_{I in rows(J)} L_IJ^T x_I)  (waits for x_I),
-//       stored in the new order and in camera order;
-//   (5) the last column to finish (ticket) runs the solve epilogue.
-// Launch boundaries become device flags: a column starts as soon as the tiles
-// it needs exist, so the factor advances along the elimination tree with no
-// per-level launch gaps.  Data crossing workgroups (L tiles, L_JJ^-1, y, x) is
-// written with sc1 (write-through) stores and read with sc1 loads; a flag is
-// raised after the writer's stores have drained (s_waitcnt + barrier) and
-// equals the solve's epoch (bumped by k_tl2_load), so flags never need clearing.
-// No residency assumption: a workgroup takes its column from a start
-// ticket, so the columns are handed out in the order the workgroups actually
-// start, and steps (1)-(3) wait only on lower columns -- workgroups that have
-// already started and cannot be descheduled.  The back substitution (4) never
-// waits on a later column: x_J is computed by the workgroup that retires the
-// LAST of J's row tiles' x (a per-column counter; the roots by their own
-// workgroup), so a column whose workgroup finished its forward part long ago,
-// or a workgroup that has not started yet, holds nothing up.  The solve is
-// therefore correct with any number of its workgroups resident (a CU-masked
-// stream, other streams' kernels holding the CUs), and bit-identical whichever
-// workgroup computes a column.  Every wait still gives up when the solve failed
-// (non-SPD tile) or after kFlowSpinMax polls (a safety net that then marks the
-// solve failed: SOLVE_FAULT), and every column is retired exactly once, so the
-// retire ticket always reaches T and its last adder runs the epilogue.
-constexpr int kFlowSpinMax = 1 << 22;  // ~0.2 s of 128-cycle polls
-#ifndef SLAM_FLOW_SLEEP
-#define SLAM_FLOW_SLEEP 2  // s_sleep between flag polls (units of 64 clocks)
-#endif
-
-#ifdef SLAM_FLOW_PROFILE
-// per column: wall clock (100 MHz) at start, diagonal updates done, factor done,
-// row tiles published, y published, x inputs in, x published, end
-__device__ unsigned long long g_flow_stamp[SLAM_TL_FLOW_MAX_T][8];
-// (stamps are kept per COLUMN: the workgroup's own column J, and (5), (6) for
-// the column k whose x it formed)
-#define FLOW_TC(col, i)                                           \
-  do {                                                            \
-    if (threadIdx.x == 0) g_flow_stamp[(col)][i] = wall_clock64(); \
-  } while (0)
-// finer stamps of the same column: first child tile in, last child tile in,
-// row 0's deferred folds done, row 0 staged, row 0's product done, row 0 published
-__device__ unsigned long long g_flow_sub[SLAM_TL_FLOW_MAX_T][8];
-// The own column's stamps go to LDS (flow_lds: 0-4 phases, 8-13 sub-stamps)
-// and out to global memory at the end, so that no stamp store is pending at
-// the phases' own s_waitcnt vmcnt(0).
-#define FLOW_LDS(i)                                               \
-  do {                                                            \
-    if (threadIdx.x == 0) flow_lds[i] = wall_clock64();           \
-  } while (0)
-#define FLOW_S(i) FLOW_LDS(8 + (i))
-#define FLOW_T(i) FLOW_LDS(i)
-#define FLOW_FLUSH()                                                             \
-  do {                                                                           \
-    if (threadIdx.x == 0) {                                                      \
-      for (int i_ = 0; i_ < 5; ++i_) g_flow_stamp[J][i_] = flow_lds[i_];         \
-      for (int i_ = 0; i_ < 6; ++i_) g_flow_sub[J][i_] = flow_lds[8 + i_];       \
-      g_flow_sub[J][6] = flow_lds[5];                                            \
-      g_flow_sub[J][7] = flow_lds[6];                                            \
-    }                                                                            \
-  } while (0)
-#else
-#define FLOW_TC(col, i) (void)0
-#define FLOW_S(i) (void)0
-#define FLOW_T(i) (void)0
-#define FLOW_FLUSH() (void)0
-#endif
-
-struct FlowPtrs {
-  int *tile, *yf, *xf, *ticket, *epoch, *start, *fail, *cnt, *dv, *pf;
-  __device__ FlowPtrs(const slam_ba_problem& p, const TlLayout& L) {
-    int* base = reinterpret_cast<int*>(p.chol + L.flow);
-    tile = base;
-    yf = base + L.T * L.T;
-    xf = yf + L.T;
-    ticket = xf + L.T;
-    epoch = ticket + 1;
-    start = ticket + 2;
-    fail = ticket + 3;  // k_tl3_flow's epoch-tagged fail word
-    cnt = ticket + 8;
-    dv = cnt + L.T;
-    pf = reinterpret_cast<int*>(p.chol + L.prod(p.tl_sched[11]));  // product slot flags
-  }
-};
-
-__device__ __forceinline__ int ld_flag(const int* f) {
-  return __hip_atomic_load(const_cast<int*>(f), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_flag(int* f, int v) {
-  __hip_atomic_store(f, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// The dataflow solve's fail word carries its solve: (epoch << 2) | code, code
-// 1 a non-SPD tile, 2 a timed-out wait -- so no launch has to clear it
-__device__ __forceinline__ int flow_fcode(const int* fail, int epoch) {
-  const int v = ld_flag(fail);
-  return (v >> 2) == epoch ? (v & 3) : 0;
-}
-__device__ __forceinline__ void flow_fail(int* fail, int epoch, int code) { st_flag(fail, (epoch << 2) | code); }
-
-// Thread 0 polls until up() holds; false (uniform) when the solve failed or
-// the wait timed out (which marks it failed).
-template <typename Up>
-__device__ __forceinline__ bool flow_poll(Up up, int epoch, int* fail, int* sh) {
-  if (threadIdx.x == 0) {
-    int ok = 1;
-    for (int spins = 0; !up(); ++spins) {
-      if (flow_fcode(fail, epoch) != 0) {
-        ok = 0;
-        break;
-      }
-      if (spins > kFlowSpinMax) {
-        flow_fail(fail, epoch, 2);
-        ok = 0;
-        break;
-      }
-      __builtin_amdgcn_s_sleep(SLAM_FLOW_SLEEP);
-    }
-    *sh = ok;
-  }
-  __syncthreads();
-  const bool ok = *sh != 0;
-  __syncthreads();
-  return ok;
-}
-// ... until *flag == epoch
-__device__ bool flow_wait(const int* flag, int epoch, int* fail, int* sh) {
-  return flow_poll([=] { return ld_flag(flag) == epoch; }, epoch, fail, sh);
-}
-// ... until the low half (retired row tiles) of column J's parent counter
-// reaches rc -- the retirers' x stores drained before their adds (the counter
-// is the acquire for those bytes)
-__device__ bool flow_wait_count(const int* cnt, int rc, int epoch, int* fail, int* sh) {
-  return flow_poll([=] { return (ld_flag(cnt) & 0xffff) >= rc; }, epoch, fail, sh);
-}
-
-// Wave 0 polls base[idx[i]] == epoch for all i < cnt together (lane i, chunks
-// of 64), so flags that are already up cost one round trip, not cnt.
-__device__ bool flow_wait_many(const int* base, const int32_t* idx, int cnt, int epoch, int* fail,
-                               int* sh) {
-  if (threadIdx.x < 64) {
-    const int lane = threadIdx.x;
-    int ok = 1;
-    for (int c0 = 0; c0 < cnt && ok; c0 += 64) {
-      const int* f = c0 + lane < cnt ? base + idx[c0 + lane] : nullptr;
-      for (int spins = 0;; ++spins) {
-        const bool up = f == nullptr || ld_flag(f) == epoch;
-        if (__all(up)) break;
-        if (flow_fcode(fail, epoch) != 0) {
-          ok = 0;
-          break;
-        }
-        if (spins > kFlowSpinMax) {
-          if (lane == 0) flow_fail(fail, epoch, 2);
-          ok = 0;
-          break;
-        }
-        __builtin_amdgcn_s_sleep(SLAM_FLOW_SLEEP);
-      }
-    }
-    if (lane == 0) *sh = ok;
-  }
-  __syncthreads();
-  const bool ok = *sh != 0;
-  __syncthreads();
-  return ok;
-}
-
-// every thread's (sc1) stores drained, then thread 0 raises the flag
-__device__ __forceinline__ void flow_publish(int* flag, int epoch) {
-  __builtin_amdgcn_s_waitcnt(0);
-  __syncthreads();
-  if (threadIdx.x == 0) st_flag(flag, epoch);
-}
-
-// tile_to_frag through sc1 loads (the tile was written by another workgroup)
-__device__ __forceinline__ void tile_to_frag_sc1(const double* __restrict__ g, int ld, double* f) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int r = lane & 15, c = lane >> 4;
-  double tmp[16];
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    const int fi = w + 4 * q;
-    tmp[q] = ld_sc1(g + (size_t)(16 * (fi >> 4) + r) * ld + 4 * (fi & 15) + c);
-  }
-#pragma unroll
-  for (int q = 0; q < 16; ++q) f[((w + 4 * q) << 6) + lane] = tmp[q];
-}
-
-// two tiles through sc1 loads, all 32 loads of a lane in flight before the LDS stores
-__device__ __forceinline__ void tiles2_to_frag_sc1(const double* __restrict__ g0, const double* __restrict__ g1,
-                                                   int ld, double* f0, double* f1) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int r = lane & 15, c = lane >> 4;
-  double t0[16], t1[16];
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    const int fi = w + 4 * q;
-    const size_t o = (size_t)(16 * (fi >> 4) + r) * ld + 4 * (fi & 15) + c;
-    t0[q] = ld_sc1(g0 + o);
-    t1[q] = ld_sc1(g1 + o);
-  }
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    f0[((w + 4 * q) << 6) + lane] = t0[q];
-    f1[((w + 4 * q) << 6) + lane] = t1[q];
-  }
-}
-
-// acc[s] += (rows 16w.., cols 16s.. of X Y^T), X and Y in fragment order
-__device__ __forceinline__ void gemm_xyT_acc(const double* Xf, const double* Yf, d4 acc[4]) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll 4
-  for (int kk = 0; kk < 16; ++kk) {
-    const double a = Xf[((w * 16 + kk) << 6) + lane];
-#pragma unroll
-    for (int s = 0; s < 4; ++s)
-      acc[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Yf[((s * 16 + kk) << 6) + lane], acc[s], 0, 0, 0);
-  }
-}
-
-// Elements of the damped tiled system gathered straight from the packed S
-// (what k_tl2_load + k_tl2_scatter lay out for the level-scheduled solve),
-// through the schedule's per-column gather tables (ba.tl_schedule): gt = the
-// tile's [64][64] packed-S offsets (-1 zero, -2 a padding row's unit
-// diagonal).  Two rounds of independent loads for all N elements (offsets,
-// then values); dg: the diagonal tile's rows of S, for lambda clamp(diag U) on
-// its diagonal (null for a row tile).
-template <int N>
-__device__ __forceinline__ void tl_gather(const double* __restrict__ sys, const int32_t* gt,
-                                          const int32_t* dg, const double* dU, double lam,
-                                          const int (&ri)[N], const int (&ci)[N], double* out) {
-  int g[N], r[N];
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    g[i] = gt[ri[i] * kTB + ci[i]];
-    r[i] = dg != nullptr && ri[i] == ci[i] ? dg[ri[i]] : -1;
-  }
-  double v[N], d[N];
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    v[i] = sys[max(g[i], 0)];
-    d[i] = r[i] >= 0 ? dU[r[i]] : 0.0;
-  }
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    double x = g[i] >= 0 ? v[i] : (g[i] == -2 ? 1.0 : 0.0);
-    if (r[i] >= 0) x += lam * clampd(d[i]);
-    out[i] = x;
-  }
-}
-
-// lower 16x16 blocks (row, column) of the diagonal update per wave of k_tl3_flow
-__constant__ int kDiagBlk[4][3][2] = {{{0, 0}, {3, 0}, {3, 1}}, {{1, 0}, {1, 1}, {3, 2}},
-                                      {{2, 0}, {2, 1}, {2, 0}}, {{2, 2}, {3, 3}, {2, 2}}};
-
-__global__ __launch_bounds__(kTlWG) __attribute__((amdgpu_waves_per_eu(1, 1)))
-void k_tl3_flow(slam_ba_problem p, int T_) {
-  lm_wave_priority();
-  const int n = 9 * p.n_cams;
-  const TlLayout L(n, T_);
-  const int32_t* S = p.tl_sched;
-  const int T = L.T;
-  const FlowPtrs F(p, L);
-  __shared__ double VX[2 * kTB * kTB];  // factor scratch; then L_JJ^-1 (fragments) | operand Y
-  __shared__ double Xf[kTB * kTB];      // operand X
-  __shared__ double part[4][kTB];
-  __shared__ double yv[kTB];
-  __shared__ double rv[kTB];
-  __shared__ int shf, okf, col_sh, ep_sh;
-  __shared__ double VR[kTB * kVR];        // L_JJ^-1 row-major (stride 65): (3), this column's x
-  __shared__ int stk[SLAM_TL_FLOW_MAX_T], sp_sh, cur_sh, last_sh, own_sh;
-#ifdef SLAM_FLOW_PROFILE
-  __shared__ unsigned long long flow_lds[16];
-#endif
-  // the column: the start ticket hands them out in the order the workgroups
-  // start.  The ticket is never reset: every solve takes exactly T tickets, so
-  // ticket v is column v mod T of solve v / T, whose number is the epoch that
-  // every flag of this solve carries (no clearing launch before the solve)
-  if (threadIdx.x == 0) {
-    const unsigned v = ticket_add(reinterpret_cast<uint32_t*>(F.start));
-    col_sh = (int)(v % (unsigned)T);
-    ep_sh = (int)(v / (unsigned)T) + 1;
-  }
-  __syncthreads();
-  const int J = col_sh;
-  const int epoch = ep_sh;
-  const int32_t* rec = S + S[5] + 5 * J;
-  const int ro = rec[0], rc = rec[1], so = rec[2], sc = rec[3], uo = rec[4];
-  // rows of the tile (its rows of S first, padding after them): the 16-row
-  // blocks of the factor
-  const int nbJ = (tl_tile_rows(S, n, T)[J] + 15) >> 4;
-  // Product tasks (ba.tl_schedule): the terms L_Ik L_Jk^T of a column J's rows
-  // 0 and 1 are formed by column k itself, as soon as both of its tiles exist,
-  // into slots that J sums after its factor -- J's diagonal phase never waits
-  // for a child's later row tiles, which its children publish after the L_Jk
-  // that phase needs.  This column's tasks (a, b, slot), ordered by b.
-  const int32_t* tkJ = S + S[S[10] + 2 * J];
-  const int n_tk = S[S[10] + 2 * J + 1];
-  double* prod = p.chol + L.prod(0);
-  // (4b)'s inputs for the cameras this column owns, loaded before any wait:
-  // thread t < 9 e_cnt takes row t % 9 of owned camera t / 9
-  const double* bvec = p.sys + sys_vec_off(p.n_cams, p.n_blocks);  // b | g | diag U | cost
-  const int cur = cur_of(p.state);
-  const double lam = p.state[SLAM_BA_ST_LAMBDA];
-  const int32_t* erJ = S + S[7] + 2 * J;
-  const int e_off = erJ[0], e_cnt = erJ[1];
-  int e_row = 0, e_rn = 0;
-  double e_cam = 0.0, e_du = 0.0, e_g = 0.0, e_cost = 0.0;
-  if (threadIdx.x < 9 * e_cnt) {
-    e_row = 9 * S[e_off + threadIdx.x / 9] + threadIdx.x % 9;
-    e_rn = tl_new_row(S, e_row);
-    e_cam = p.cams[cur][e_row];
-    e_g = bvec[n + e_row];
-    e_du = bvec[2 * n + e_row];
-  }
-  if (threadIdx.x < e_cnt) e_cost = bvec[3 * n + S[e_off + threadIdx.x]];
-  const int own_orow = threadIdx.x < kTB ? tl_old_row(S, n, J * kTB + threadIdx.x) : -1;
-  const double b_own = own_orow >= 0 ? bvec[own_orow] : 0.0;  // b_J in the tiled order (3)
-  int* fail = F.fail;
-  // this column's parent counter, re-armed before any tile of J is published:
-  // no row tile of J can retire before J's tiles exist (x_I needs L_IJ)
-  if (threadIdx.x == 0) st_flag(F.cnt + J, 0);
-  // this column's gather tables: its diagonal tile, row tile q at 1 + q, the
-  // diagonal tile's rows of S after them
-  const int32_t* gtJ = S + S[S[9] + J];
-  const int32_t* dgJ = gtJ + (1 + rc) * kTB * kTB;
-  const double* dU = bvec + 2 * n;
-  double* A = p.chol + L.a;
-  double* Vf = VX;
-  double* Yf = VX + kTB * kTB;
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  bool ok = true;
-  FLOW_T(0);
-  // The diagonal update is symmetric and the factor reads only lower blocks:
-  // the 10 lower 16x16 blocks, three per wave (waves 2 and 3 repeat one block
-  // they do not store), so each SIMD's MFMA chain per child tile is 48 steps
-  // instead of 64.
-  int dR[3], dC[3];
-#pragma unroll
-  for (int b = 0; b < 3; ++b) {
-    dR[b] = kDiagBlk[w][b][0];
-    dC[b] = kDiagBlk[w][b][1];
-  }
-  const int dnb = w < 2 ? 3 : 2;
-  // A_JJ's blocks, gathered from the packed system into registers before any
-  // wait (no load / scatter launch before the solve)
-  double ajj[12];
-  {
-    int gi[12], gj[12];
-#pragma unroll
-    for (int b = 0; b < 3; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        gi[4 * b + r] = dR[b] * 16 + (lane >> 4) + 4 * r;
-        gj[4 * b + r] = dC[b] * 16 + (lane & 15);
-      }
-    tl_gather<12>(p.sys, gtJ, dgJ, dU, lam, gi, gj, ajj);
-  }
-  // ... and the first two row tiles' A_IJ
-  double air[2][16];
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    int gi[16], gj[16];
-#pragma unroll
-    for (int s2 = 0; s2 < 4; ++s2)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        gi[4 * s2 + r] = w * 16 + (lane >> 4) + 4 * r;
-        gj[4 * s2 + r] = s2 * 16 + (lane & 15);
-      }
-    tl_gather<16>(p.sys, gtJ + (q < rc ? 1 + q : 0) * kTB * kTB, nullptr, dU, lam, gi, gj, air[q]);
-  }
-  // (1) diagonal tile, child tiles k in rs order: L_Jk operands double-buffered
-  // (Xf / VX[4096:]); the next child's tile is fetched before this one's MFMAs
-  // when its flag is already up (loads in flight under the MFMAs), after them
-  // otherwise (a child that is not ready yet never holds up the MFMAs of the
-  // ones that are).  Row tiles 0 and 1 take their updates from the product
-  // slots after the factor (2).
-  d4 acc[4];
-#pragma unroll
-  for (int s2 = 0; s2 < 4; ++s2) acc[s2] = d4{0.0, 0.0, 0.0, 0.0};
-  // The buffers alternate so that the LAST child's L_Jk lands in Xf.
-  if (sc > 0) {
-    ok = flow_wait(F.tile + J * T + S[so], epoch, fail, &shf);
-    if (ok) tile_to_frag_sc1(A + (size_t)J * kTB * L.N + S[so] * kTB, L.N, ((sc - 1) & 1) ? Yf : Xf);
-    FLOW_S(0);
-  }
-  for (int q = 0; q < sc && ok; ++q) {
-    double* cur = ((sc - 1 - q) & 1) ? Yf : Xf;
-    double* nxt = ((sc - 1 - q) & 1) ? Xf : Yf;
-    __syncthreads();  // cur filled; the previous MFMAs' reads of nxt done
-    if (q == sc - 1) FLOW_S(1);
-    bool pre = false;
-    if (q + 1 < sc) {
-      if (t == 0) shf = ld_flag(F.tile + J * T + S[so + q + 1]) == epoch ? 1 : 0;
-      __syncthreads();
-      pre = shf != 0;
-      __syncthreads();
-      if (pre) tile_to_frag_sc1(A + (size_t)J * kTB * L.N + S[so + q + 1] * kTB, L.N, nxt);
-    }
-#pragma unroll 4
-    for (int kk = 0; kk < 16; ++kk)
-#pragma unroll
-      for (int b = 0; b < 3; ++b)
-        acc[b] = __builtin_amdgcn_mfma_f64_16x16x4f64(cur[((dR[b] * 16 + kk) << 6) + lane],
-                                                      cur[((dC[b] * 16 + kk) << 6) + lane], acc[b], 0, 0, 0);
-    if (q + 1 < sc) {
-      if (!pre) {
-        ok = flow_wait(F.tile + J * T + S[so + q + 1], epoch, fail, &shf);
-        if (ok) tile_to_frag_sc1(A + (size_t)J * kTB * L.N + S[so + q + 1] * kTB, L.N, nxt);
-      }
-    }
-  }
-  __syncthreads();
-  FLOW_T(1);
-  if (ok) {
-    double* M = VX;  // lower blocks only (tile_chol_inv_blk reads no others)
-#pragma unroll
-    for (int b = 0; b < 3; ++b)
-      if (b < dnb) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = dR[b] * 16 + (lane >> 4) + 4 * r, col = dC[b] * 16 + (lane & 15);
-          M[row * kMS + col] = ajj[4 * b + r] - acc[b][r];
-        }
-      }
-    double* Xb = VX + kTB * kMS;
-    ok = tile_chol_inv_blk(nullptr, 0, M, Xb, Xb + 10 * 16 * kBS17, &okf, nbJ);
-    // L_JJ^-1 out of the block store into (swizzled) fragment order (Vf) and
-    // row-major (VR): wave w takes rows [16w, 16w + 16), lane = column
-    double x[16];
-    if (ok) {
-      const int cb16 = lane >> 4;
-#pragma unroll
-      for (int m = 0; m < 16; ++m)
-        x[m] = w >= cb16 ? Xb[blk_id(w, cb16) * 16 * kBS17 + m * kBS17 + (lane & 15)] : 0.0;
-    }
-    __syncthreads();  // VX is reused below
-    if (!ok) {
-      if (t == 0) flow_fail(fail, epoch, 1);
-    } else {
-#pragma unroll
-      for (int m = 0; m < 16; ++m) {
-        Vf[frag_swz(16 * w + m, lane)] = x[m];
-        VR[(16 * w + m) * kVR + lane] = x[m];
-      }
-    }
-    __syncthreads();
-  }
-  FLOW_T(2);
-  // (2) row tiles, parent first.  Rows 0 and 1 (the children folded in during
-  // (1), A_IJ in registers) and the rest are separate straight-line instances:
-  // one uniform branch per row tile, not one per element (this code runs once
-  // per solve on a CU whose instruction cache the LM kernels have refilled, so
-  // every taken branch into cold code costs an L2 fetch).
-  double l0[16];  // L_{rows[0]} J, kept for this column's product tasks with a = 0
-  auto row_tile = [&](auto QC, int q) {
-    constexpr int qc = decltype(QC)::value;  // 0, 1: rows 0 / 1; 2: any later row
-    const int I = S[ro + q];
-    const int ko = S[uo + 2 * q], kc = S[uo + 2 * q + 1];
-#pragma unroll
-    for (int s2 = 0; s2 < 4; ++s2) acc[s2] = d4{0.0, 0.0, 0.0, 0.0};
-    // Rows 0 and 1: the k list's product slots (after the list), summed in list
-    // order, each a 64x64 term in the accumulator layout; the staged A_IJ goes
-    // to Yf.  Later rows load both tiles (loads in flight together), MFMA the
-    // term here and stage into Xf.
-    double* stg = qc < 2 ? Yf : Xf;
-    if constexpr (qc < 2) {
-      if (kc > 0) ok = flow_wait_many(F.pf, S + ko + kc, kc, epoch, fail, &shf);
-#ifdef SLAM_FLOW_PROFILE
-      if (q == 0) FLOW_LDS(5);
-#endif
-      for (int u0 = 0; u0 < kc && ok; u0 += 2) {
-        double cv[2][16];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const double* Cp = prod + (size_t)S[ko + kc + min(u0 + h, kc - 1)] * kTB * kTB;
-#pragma unroll
-          for (int e = 0; e < 16; ++e) cv[h][e] = ld_sc1(Cp + ((4 * w + (e >> 2)) * 4 + (e & 3)) * 64 + lane);
-        }
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-          if (u0 + h < kc) {
-#pragma unroll
-            for (int s2 = 0; s2 < 4; ++s2)
-#pragma unroll
-              for (int r = 0; r < 4; ++r) acc[s2][r] += cv[h][4 * s2 + r];
-          }
-      }
-#ifdef SLAM_FLOW_PROFILE
-      if (q == 0) FLOW_LDS(6);
-#endif
-    } else {
-      for (int u = 0; u < kc && ok; ++u) {
-        const int k = S[ko + u];
-        ok = flow_wait(F.tile + I * T + k, epoch, fail, &shf);  // (J, k) was waited for in (1)
-        if (!ok) break;
-        tiles2_to_frag_sc1(A + (size_t)I * kTB * L.N + k * kTB, A + (size_t)J * kTB * L.N + k * kTB, L.N,
-                           Yf, Xf);
-        __syncthreads();
-        gemm_xyT_acc(Yf, Xf, acc);
-        __syncthreads();
-      }
-    }
-    if (!ok) return;
-    if (q == 0) FLOW_S(2);
-    double* AIJ = A + (size_t)I * kTB * L.N + J * kTB;
-    double a[16];
-    if constexpr (qc < 2) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) a[e] = air[qc][e];
-    } else {
-      int gi[16], gj[16];
-#pragma unroll
-      for (int s2 = 0; s2 < 4; ++s2)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          gi[4 * s2 + r] = w * 16 + (lane >> 4) + 4 * r;
-          gj[4 * s2 + r] = s2 * 16 + (lane & 15);
-        }
-      tl_gather<16>(p.sys, gtJ + (1 + q) * kTB * kTB, nullptr, dU, lam, gi, gj, a);
-    }
-#pragma unroll
-    for (int s2 = 0; s2 < 4; ++s2)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = w * 16 + (lane >> 4) + 4 * r, col = s2 * 16 + (lane & 15);
-        stg[frag_swz(row, col)] = a[4 * s2 + r] - acc[s2][r];
-      }
-    __syncthreads();
-    if (q == 0) FLOW_S(3);
-    d4 lacc[4];
-    gemm_xyT_lowY_swz(stg, Vf, lacc);  // L_IJ = A_IJ (L_JJ^-1)^T
-#ifdef SLAM_FLOW_PROFILE
-    if (q == 0) {
-      __builtin_amdgcn_s_waitcnt(0);
-      FLOW_S(4);
-    }
-#endif
-#pragma unroll
-    for (int s2 = 0; s2 < 4; ++s2)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = w * 16 + (lane >> 4) + 4 * r, col = s2 * 16 + (lane & 15);
-        st_sc1(AIJ + (size_t)row * L.N + col, lacc[s2][r]);
-      }
-    flow_publish(F.tile + I * T + J, epoch);
-    if (q == 0) FLOW_S(5);
-    if (q == 0) {
-#pragma unroll
-      for (int s2 = 0; s2 < 4; ++s2)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) l0[4 * s2 + r] = lacc[s2][r];
-    }
-    // this column's product tasks with b = q: L_IJ (this row tile, X operand)
-    // times L_{rows[a]} J^T (row 0 from registers, others reloaded), into the
-    // slot; the publish's barrier ended every read of Xf / Yf
-    bool xs = false;
-    for (int e = 0; e < n_tk; ++e) {
-      if (tkJ[3 * e + 1] != q) continue;  // (uniform)
-      const int ta = tkJ[3 * e], slot = tkJ[3 * e + 2];
-      if (!xs) {
-#pragma unroll
-        for (int s2 = 0; s2 < 4; ++s2)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            Xf[frag_idx(w * 16 + (lane >> 4) + 4 * r, s2 * 16 + (lane & 15))] = lacc[s2][r];
-        xs = true;
-      }
-      if (ta == 0) {
-#pragma unroll
-        for (int s2 = 0; s2 < 4; ++s2)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            Yf[frag_idx(w * 16 + (lane >> 4) + 4 * r, s2 * 16 + (lane & 15))] = l0[4 * s2 + r];
-      } else {
-        tile_to_frag_sc1(A + (size_t)S[ro + ta] * kTB * L.N + J * kTB, L.N, Yf);
-      }
-      __syncthreads();
-      d4 pacc[4];
-#pragma unroll
-      for (int s2 = 0; s2 < 4; ++s2) pacc[s2] = d4{0.0, 0.0, 0.0, 0.0};
-      gemm_xyT_acc(Xf, Yf, pacc);
-      double* Cp = prod + (size_t)slot * kTB * kTB;
-#pragma unroll
-      for (int s2 = 0; s2 < 4; ++s2)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) st_sc1(Cp + ((4 * w + s2) * 4 + r) * 64 + lane, pacc[s2][r]);
-      flow_publish(F.pf + slot, epoch);  // (its barrier also ends this task's Yf reads)
-    }
-  };
-  if (ok && rc > 0) row_tile(std::integral_constant<int, 0>{}, 0);
-  if (ok && rc > 1) row_tile(std::integral_constant<int, 1>{}, 1);
-  for (int q = 2; q < rc && ok; ++q) row_tile(std::integral_constant<int, 2>{}, q);
-  FLOW_T(3);
-  // (3) forward substitution: r = b_J - sum_{k in rs(J)} L_Jk y_k, the terms
-  // pushed by the children (fc[J][k]); y_J = L_JJ^-1 r; then this column's
-  // own terms L_IJ y_J for its rows I (fc[I][J]), published with the y flag
-  if (ok) ok = flow_wait_many(F.yf, S + so, sc, epoch, fail, &shf);
-  if (ok) {
-    if (t < kTB) {
-      double r = b_own;
-      for (int q0 = 0; q0 < sc; q0 += 16) {
-        double v[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u)
-          v[u] = q0 + u < sc ? ld_sc1(p.chol + L.fc + ((size_t)J * T + S[so + q0 + u]) * kTB + t) : 0.0;
-#pragma unroll
-        for (int u = 0; u < 16; ++u)
-          if (q0 + u < sc) r -= v[u];
-      }
-      rv[t] = r;
-    }
-    __syncthreads();
-    // y_J[m] = sum_c L_JJ^-1[m][c] r[c]: thread (w, m) sums c in [16w, 16w + 16)
-    double s3 = 0.0;
-    for (int c = 16 * w; c < 16 * w + 16; ++c) s3 = __builtin_fma(VR[lane * kVR + c], rv[c], s3);
-    part[w][lane] = s3;
-    __syncthreads();
-    if (t < kTB) yv[t] = ((part[0][t] + part[1][t]) + part[2][t]) + part[3][t];
-    __syncthreads();
-    for (int q = 0; q < rc; ++q) {
-      const int I = S[ro + q];
-      const double* LIJ = A + (size_t)(I * kTB + lane) * L.N + J * kTB + 16 * w;
-      double la[16];
-#pragma unroll
-      for (int c = 0; c < 16; ++c) la[c] = ld_sc1(LIJ + c);
-      double s4 = 0.0;
-#pragma unroll
-      for (int c = 0; c < 16; ++c) s4 = __builtin_fma(la[c], yv[16 * w + c], s4);
-      part[w][lane] = s4;
-      __syncthreads();
-      if (t < kTB)
-        st_sc1(p.chol + L.fc + ((size_t)I * T + J) * kTB + t,
-               ((part[0][t] + part[1][t]) + part[2][t]) + part[3][t]);
-      __syncthreads();
-    }
-    flow_publish(F.yf + J, epoch);
-  }
-  FLOW_T(4);
-  // (4) back substitution: x_k = L_kk^-T (y_k - sum_I L_Ik^T x_I) over the row
-  // tiles I of column k (thread (w, c = lane) sums rows [16w, 16w + 16) of every
-  // I in row order; the operations and their order do not depend on which
-  // workgroup forms x_k).  Who forms x_J:
-  //   a root (no row tiles): this workgroup, right away;
-  //   otherwise, once every workgroup of the grid has started (the start ticket
-  //   reached T: waiting can then hold up no one), this workgroup registers as
-  //   the waiter on cnt[J] (+2^16) and forms x_J when its row tiles' x are all
-  //   retired -- unless the last of them was retired before it registered;
-  //   else the workgroup that retires the last row tile of J (cnt[J] reaches
-  //   rows(J) with no waiter registered) pushes J on its own stack.
-  // So the columns run in parallel when the grid is resident, and a column whose
-  // workgroup cannot wait is still formed.  Every column is retired once: x
-  // flag, its children's counters, the retire ticket.
-  if (t == 0) {
-    sp_sh = 0;
-    last_sh = 0;
-    own_sh = 0;
-    if (rc == 0) {
-      own_sh = 1;
-    } else if (ld_flag(F.start) >= epoch * T) {  // every workgroup of this solve has started
-      const unsigned old = __hip_atomic_fetch_add(reinterpret_cast<unsigned*>(F.cnt + J), 1u << 16,
-                                                  __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      own_sh = (int)(old & 0xffffu) < rc ? 2 : 0;
-    }
-  }
-  __syncthreads();
-  if (!own_sh) {
-    // another workgroup forms x_J: L_JJ^-1 and y_J for it, published by dv[J]
-    double* V = p.chol + L.dinv + (size_t)J * kTB * kTB;
-    for (int e = t; e < kTB * kTB; e += kTlWG) st_sc1(V + e, VR[(e >> 6) * kVR + (e & 63)]);
-    if (t < kTB) st_sc1(p.chol + L.y + J * kTB + t, yv[t]);
-    flow_publish(F.dv + J, epoch);
-  }
-  // the own column's first two L_IJ in flight before its wait (they are this
-  // workgroup's own stores of (2)): only x_I is loaded after the counter
-  double la_pre[2][16];
-  if (own_sh == 2) {
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-      if (q < rc) {
-        const double* LIk = A + (size_t)(S[ro + q] * kTB + 16 * w) * L.N + J * kTB + lane;
-#pragma unroll
-        for (int m = 0; m < 16; ++m) la_pre[q][m] = ld_sc1(LIk + (size_t)m * L.N);
-      }
-  }
-  for (int it = 0;; ++it) {
-    int k;
-    bool okk;
-    if (it == 0) {  // this workgroup's own column, when it forms it
-      if (!own_sh) continue;
-      k = J;
-      okk = ok && (own_sh == 1 || flow_wait_count(F.cnt + J, rc, epoch, fail, &shf));
-    } else {
-      if (t == 0) cur_sh = sp_sh > 0 ? stk[--sp_sh] : -1;
-      __syncthreads();
-      k = cur_sh;
-      if (k < 0) break;
-      okk = flow_wait(F.dv + k, epoch, fail, &shf);
-    }
-    const bool own = k == J;
-    const int32_t* rk = S + S[5] + 5 * k;
-    const int kro = rk[0], krc = rk[1], kso = rk[2], ksc = rk[3];
-    // x_k's rows in camera order: loaded before the waits below, off the chain
-    const int orow = own ? own_orow : (t < kTB ? tl_old_row(S, n, k * kTB + t) : -1);
-    if (okk) {
-      if (!own && t < kTB) yv[t] = ld_sc1(p.chol + L.y + k * kTB + t);
-      double s2 = 0.0;
-      for (int q = 0; q < krc; ++q) {
-        const int I = S[kro + q];
-        const double* LIk = A + (size_t)(I * kTB + 16 * w) * L.N + k * kTB + lane;
-        const double* xI = p.chol + L.x + I * kTB + 16 * w;
-        double la[16], xa[16];
-        const bool pre = it == 0 && own_sh == 2 && q < 2;  // (uniform)
-#pragma unroll
-        for (int m = 0; m < 16; ++m) {
-          la[m] = pre ? (q == 0 ? la_pre[0][m] : la_pre[1][m]) : ld_sc1(LIk + (size_t)m * L.N);
-          xa[m] = ld_sc1(xI + m);
-        }
-#pragma unroll
-        for (int m = 0; m < 16; ++m) s2 = __builtin_fma(la[m], xa[m], s2);
-      }
-      FLOW_TC(k, 5);
-      part[w][lane] = s2;
-      __syncthreads();
-      if (t < kTB) rv[t] = yv[t] - (((part[0][t] + part[1][t]) + part[2][t]) + part[3][t]);
-      __syncthreads();
-      double s3 = 0.0;  // x_k[c] = sum_m L_kk^-1[m][c] r[m]
-      if (own) {
-        for (int m = 16 * w; m < 16 * w + 16; ++m) s3 = __builtin_fma(VR[m * kVR + lane], rv[m], s3);
-      } else {
-        const double* Vk = p.chol + L.dinv + (size_t)k * kTB * kTB;
-        for (int m = 16 * w; m < 16 * w + 16; ++m) s3 = __builtin_fma(ld_sc1(Vk + m * kTB + lane), rv[m], s3);
-      }
-      __syncthreads();  // rv / part reads done before part is rewritten
-      part[w][lane] = s3;
-      __syncthreads();
-      if (t < kTB) {
-        const double xv = ((part[0][t] + part[1][t]) + part[2][t]) + part[3][t];
-        Xf[t] = xv;  // (4b) (Xf is free after (2))
-        st_sc1(p.chol + L.x + k * kTB + t, xv);
-        if (orow >= 0) st_sc1(p.chol + L.xo + orow, xv);  // camera order (padding rows dropped)
-      }
-    }
-    // retire column k even when the solve failed (the counters and the ticket
-    // still complete; the epilogue sees the fail code)
-    flow_publish(F.xf + k, epoch);
-    FLOW_TC(k, 6);
-    // the parent counters (one lane each) in flight together -- independent,
-    // and a chain of returning atomics cost a device round trip each on the
-    // back substitution's critical path; the columns this retire completes go
-    // on the stack in u order
-    if (t < 64) {
-      for (int u0 = 0; u0 == 0 || u0 < ksc; u0 += 64) {
-        const int u = u0 + t;
-        int c = 0, rcc = 0;
-        unsigned old = 0;
-        if (u < ksc) {
-          c = S[kso + u];  // k is a row tile of column c
-          rcc = S[S[5] + 5 * c + 1];
-          old = ticket_add(reinterpret_cast<uint32_t*>(F.cnt + c));
-        }
-        const bool push = u < ksc && (int)(old & 0xffffu) == rcc - 1 && (old >> 16) == 0;
-        const unsigned long long m = __ballot(push);
-        const int base = sp_sh;
-        if (push) stk[base + __popcll(m & ((1ull << t) - 1ull))] = c;
-        wave_lds_fence();
-        if (t == 0) sp_sh = base + __popcll(m);
-        wave_lds_fence();
-      }
-    }
-    // (4b) the epilogue of the cameras tile k owns (ba.tl_schedule: those whose
-    // lowest tile is k -- every other tile of a camera is a row tile of k, so
-    // its x is already out), after the retire so that no child waits on it:
-    // delta_c, the trial parameters cams[1-cur] and their projection records,
-    // this tile's share of the camera part of the predicted reduction and of
-    // the cost (fixed order) into epi[k]; the same operations whichever
-    // workgroup forms x_k.  Written through (sc1) and drained before the retire
-    // ticket, so that the last retirer's failure path overwrites them safely.
-    {
-      const bool mine = own && own_sh != 0;
-      const int32_t* er = S + S[7] + 2 * k;
-      const int eo = mine ? e_off : er[0], ec = mine ? e_cnt : er[1];
-      double* ct = Xf + kTB;                  // trial parameters [ec][9]
-      double* pv = ct + 9 * kEpiCams;         // pc terms [9 ec]
-      double* cv = pv + 9 * kEpiCams;         // cost terms [ec]
-      if (t < 9 * ec) {
-        int row = e_row, rn = e_rn;
-        double cam = e_cam, du = e_du, g = e_g;
-        if (!mine) {
-          row = 9 * S[eo + t / 9] + t % 9;
-          rn = tl_new_row(S, row);
-          cam = p.cams[cur][row];
-          g = bvec[n + row];
-          du = bvec[2 * n + row];
-        }
-        const double d = (rn >> 6) == k ? Xf[rn & 63] : ld_sc1(p.chol + L.xo + row);
-        st_sc1(p.delta_c + row, d);
-        const double tr = cam + d;
-        st_sc1(p.cams[1 - cur] + row, tr);
-        ct[t] = tr;
-        pv[t] = d * (lam * clampd(du) * d + g);
-      }
-      if (t < ec) cv[t] = mine ? e_cost : bvec[3 * n + S[eo + t]];
-      __syncthreads();
-      if (t < ec) {
-        double rec[kCamRec];
-        cam_prep(ct + 9 * t, rec);
-        double* o = p.camrec[1 - cur] + kCamRec * S[eo + t];
-#pragma unroll
-        for (int i = 0; i < kCamRec; ++i) st_sc1(o + i, rec[i]);
-      }
-      if (t == 0) {
-        double pc = 0.0, cs = 0.0;
-        for (int i = 0; i < 9 * ec; ++i) pc += pv[i];
-        for (int q = 0; q < ec; ++q) cs += cv[q];
-        st_sc1(p.chol + L.epi + 2 * k, pc);
-        st_sc1(p.chol + L.epi + 2 * k + 1, cs);
-      }
-      __builtin_amdgcn_s_waitcnt(0);
-      __syncthreads();
-      // (never reset: T retires per solve, the last of each solve is T - 1 mod T)
-      if (t == 0 && ticket_add(reinterpret_cast<uint32_t*>(F.ticket)) % (unsigned)T == (unsigned)(T - 1))
-        last_sh = 1;
-    }
-    __syncthreads();
-  }
-  FLOW_FLUSH();
-  // (5) the workgroup that retired the last column (after its epilogue share)
-  // sums the per-tile partials in tile order; after a failed solve it redoes
-  // the whole epilogue with a zero step instead (its plain stores land after
-  // the shares' drained write-through stores)
-  if (!last_sh) return;
-#ifdef SLAM_FLOW_PROFILE
-  if (t == 0) g_flow_epi[0] = wall_clock64();
-#endif
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  const int fcode = flow_fcode(fail, epoch);  // 0 ok, 1 non-SPD tile, 2 a wait timed out
-  if (fcode != 0) {
-    const double* gvec = bvec + n;
-    solve_epilogue<true>(p, p.chol + L.xo, false, &part[0][0],
-                         EpiSrc{gvec, bvec + 2 * n, p.cams[cur], gvec + 2 * n}, fcode);
-  } else if (t < 64) {
-    double pc = 0.0, cs = 0.0;  // lane t: tiles t, t + 64, ...; then a fixed shuffle tree
-    for (int k = t; k < T; k += 64) {
-      pc += ld_sc1(p.chol + L.epi + 2 * k);
-      cs += ld_sc1(p.chol + L.epi + 2 * k + 1);
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-      pc += __shfl_down(pc, off, 64);
-      cs += __shfl_down(cs, off, 64);
-    }
-    if (t == 0) {
-      p.state[SLAM_BA_ST_COST] = 0.5 * cs;
-      p.state[SLAM_BA_ST_PRED_CAM] = 0.5 * pc;
-      p.state[SLAM_BA_ST_CHOL_FAIL] = 0.0;
-    }
-  }
-#ifdef SLAM_FLOW_PROFILE
-  __builtin_amdgcn_s_waitcnt(0);
-  __syncthreads();
-  if (t == 0) g_flow_epi[3] = wall_clock64();
-#endif
-  FLOW_TC(J, 7);
-}
-
-// The dataflow solve makes no residency assumption (k_tl3_flow's comment), so it
-// runs on any stream, CU-masked or not, beside any other work.  It needs the
-// column count within its LDS stack (SLAM_TL_FLOW_MAX_T, < 2^16 for the parent
-// counters) and the camera-order x of the epilogue in its LDS scratch;
-// otherwise (or with tl_mode "levels") the level-scheduled launches run.
-static bool tl_flow_ok(const slam_ba_problem& p, hipStream_t) {
-  if (p.tl_mode != 0 || p.tl_sched_host == nullptr || p.tl_sched_host[5] <= 0) return false;
-  const TlLayout L(9 * p.n_cams, p.tl_sched_host[1]);
-  return L.T <= SLAM_TL_FLOW_MAX_T && 9 * p.n_cams <= 2 * kTB * kTB;
-}
-
-// k_tl2_load over the structural tiles when the schedule carries the column table
-static void tl_load(const slam_ba_problem& p, hipStream_t s) {
-  const int32_t* h = p.tl_sched_host;
-  const int T = h[1];
-  if (h[5] > 0) {
-    int maxrc = 0;
-    for (int J = 0; J < T; ++J) maxrc = std::max(maxrc, (int)h[h[5] + 5 * J + 1]);
-    k_tl2_load<<<dim3(T, 1 + maxrc), kTlWG, 0, s>>>(p, T, 1);
-  } else {
-    k_tl2_load<<<T * (T + 1) / 2, kTlWG, 0, s>>>(p, T, 0);
-  }
-}
-
-// the layout the kernels assume (row maps at fixed offsets after the header,
-// every row of S in some tile)
-static int tl_check_sched(const slam_ba_problem& p) {
-  const int32_t* h = p.tl_sched_host;
-  const int n = 9 * p.n_cams, T = h[1];
-  SLAM_REQUIRE(T >= (n + kTB - 1) / kTB && h[2] == kTlHdr && h[3] == kTlHdr + n &&
-                   h[6] == kTlHdr + n + T * kTB && h[8] > 0 && h[9] > 0 && h[10] > h[9] && h[11] >= 0,
-               "slam_ba: tl_sched layout is not ba.tl_schedule's (T %d, offsets %d %d %d for n %d)", T,
-               h[2], h[3], h[6], n);
-  return SLAM_OK;
-}
-
-static int tl_solve_flow(const slam_ba_problem& p, hipStream_t s) {
-  const TlLayout L(9 * p.n_cams, p.tl_sched_host[1]);
-  if (int rc = tl_check_sched(p)) return rc;
-  k_tl3_flow<<<L.T, kTlWG, 0, s>>>(p, L.T);  // gathers its tiles from the packed system itself
-  SLAM_LAUNCHED("k_tl3_flow");
-  return SLAM_OK;
-}
-
-static int tl_solve_levels(const slam_ba_problem& p, hipStream_t s) {
-  const TlLayout L(9 * p.n_cams, p.tl_sched_host[1]);
-  const int32_t* h = p.tl_sched_host;
-  const int nlev = h[0], T = h[1];
-  if (int rc = tl_check_sched(p)) return rc;
-  const int32_t* tab = h + h[4];
-  tl_load(p, s);
-  k_tl2_scatter<<<p.n_blocks, 128, 0, s>>>(p, L.T);
-  for (int lv = 0; lv < nlev; ++lv) {
-    const int32_t* e = tab + 6 * lv;
-    if (e[1] > 0) k_tl2_panel<<<e[1], kTlWG, 0, s>>>(p, T, e[0]);
-    if (e[3] > 0) k_tl2_update<<<e[3], kTlWG, 0, s>>>(p, T, e[2]);
-  }
-  for (int lv = nlev - 1; lv >= 0; --lv) {
-    const int32_t* e = tab + 6 * lv;
-    if (e[5] > 0) k_tl2_back<<<e[5], kTlWG, 0, s>>>(p, T, e[4]);
-  }
-  k_tl2_unperm<<<T, kTB, 0, s>>>(p, T);
-  k_tl2_epilogue<<<1, 1024, 0, s>>>(p, T);
-  SLAM_LAUNCHED("k_tl2_*");
-  return SLAM_OK;
-}
-
 __device__ void lm_decide(double* __restrict__ state, const double* __restrict__ small);
 
 // Back substitution + trial cost, one workgroup per point group:
@@ -2981,7 +1426,6 @@ __global__ void k_reset(BaBatch bat, double lam0) {
   for (int c = t; c < p.n_cams; c += blockDim.x) cam_prep(p.cams[0] + 9 * c, p.camrec[0] + kCamRec * c);
 }
 
-inline int nblk(int n, int bs) { return (n + bs - 1) / bs; }
 
 int check_problem(const slam_ba_problem* p) {
   SLAM_REQUIRE(p != nullptr, "slam_ba: null problem");
@@ -3030,16 +1474,6 @@ extern "C" int slam_ba_red_slots(int n_grps) { return 2 * n_grps; }
 
 extern "C" int slam_ba_problem_size(void) { return (int)sizeof(slam_ba_problem); }
 
-extern "C" long long slam_ba_chol_len(int n_cams, const int32_t* tl_sched_host) {
-  // tiled factor workspace (9C > kLdsMaxN) for a schedule of tl_sched_host[1]
-  // tiles and tl_sched_host[11] product slots; no schedule: the fewest 64-row
-  // tiles that hold 9C rows, no slots
-  if (n_cams <= 0) return 0;
-  const int n = 9 * n_cams;
-  if (tl_sched_host == nullptr) return TlLayout(n, (n + kTB - 1) / kTB).total;
-  return TlLayout(n, tl_sched_host[1]).with_slots(tl_sched_host[11]);
-}
-
 extern "C" long long slam_ba_sys_len(int n_cams, int n_blocks) {
   const long long c9 = 9ll * n_cams;
   return sys_vec_off(n_cams, n_blocks) + 3 * c9 + n_cams;
@@ -3079,7 +1513,15 @@ namespace {
 // pivot chain off CUs whose SIMDs are busy with ORB waves.
 static size_t g_solve_lds_floor = 0;
 
-static int make_launch(const slam_ba_problem* probs, int n, Launch* L) {
+static int launch_reset(const Launch& L, double lam0, hipStream_t s) {
+  k_reset<<<dim3(1, L.n), 64, 0, s>>>(L.b, lam0);
+  SLAM_LAUNCHED("k_reset");
+  return SLAM_OK;
+}
+
+}  // namespace
+
+int slam::make_launch(const slam_ba_problem* probs, int n, Launch* L) {
   SLAM_REQUIRE(n >= 1 && n <= kBaMaxBatch, "slam_ba: batch of %d problems (1..%d)", n, kBaMaxBatch);
   SLAM_REQUIRE(probs != nullptr, "slam_ba: null problem array");
   L->n = n;
@@ -3109,13 +1551,7 @@ static int make_launch(const slam_ba_problem* probs, int n, Launch* L) {
   return SLAM_OK;
 }
 
-static int launch_reset(const Launch& L, double lam0, hipStream_t s) {
-  k_reset<<<dim3(1, L.n), 64, 0, s>>>(L.b, lam0);
-  SLAM_LAUNCHED("k_reset");
-  return SLAM_OK;
-}
-
-static int launch_build(const Launch& L, hipStream_t s) {
+int slam::launch_build(const Launch& L, hipStream_t s) {
   // every entry of sys is written by the assembly (all listed blocks), so no clearing
   bool folded = L.mode == 1;
   for (int i = 0; i < L.n; ++i) folded = folded && L.b.p[i].asm_tab != nullptr;
@@ -3135,16 +1571,10 @@ static int launch_build(const Launch& L, hipStream_t s) {
   return SLAM_OK;
 }
 
+namespace {
+
 static int launch_solve(const Launch& L, bool fuse_decide, hipStream_t s) {
-  if (L.dense) {
-    if (int rc = slam::launch_solve_blk(L, s)) return rc;
-  } else {
-    if (tl_flow_ok(L.b.p[0], s)) {
-      if (int rc = tl_solve_flow(L.b.p[0], s)) return rc;
-    } else {
-      if (int rc = tl_solve_levels(L.b.p[0], s)) return rc;
-    }
-  }
+  if (int rc = L.dense ? slam::launch_solve_blk(L, s) : slam::launch_solve_tiled(L.b.p[0], s)) return rc;
   if (L.robust) {
     if (fuse_decide) k_back_trial<true, true><<<dim3(L.max_grps, L.n), kGrp, 0, s>>>(L.b);
     else k_back_trial<false, true><<<dim3(L.max_grps, L.n), kGrp, 0, s>>>(L.b);
@@ -3233,702 +1663,10 @@ extern "C" int slam_ba_iterate_batch(const slam_ba_problem* probs, int n_probs, 
   return SLAM_OK;
 }
 
-// ---------------------------------------------------------------- camera covariance
-// Marginal covariance of the camera parameters: 9x9 blocks of S0^-1, S0 the
-// reduced camera system at lambda = 0.  The build runs unchanged
-// between two one-lane kernels that park lambda; S0 is gathered into lower
-// 64x64 tiles of a dense matrix in natural camera order (held and padding rows:
-// unit diagonal, no coupling), factored by a blocked right-looking Cholesky over
-// tile columns (k_cov_panel / k_cov_update, the tile factor of the tiled
-// solve), L^-1 formed by tile rows (k_cov_minv), and the requested tiles of
-// L^-T L^-1 (k_cov_sigma) picked into the output blocks (k_cov_pick).  Not a
-// per-iteration path: one workgroup per tile, O(T) launches, nothing resident.
-namespace {
-
-struct CovLayout {  // doubles inside the workspace; T = ceil(9C / 64)
-  int T, N;
-  long long a, m, diag, need, hdr, total;
-  __host__ __device__ explicit CovLayout(int n_cams) {
-    T = (9 * n_cams + kTB - 1) / kTB;
-    N = T * kTB;
-    a = 0;                              // S0 -> L (lower tiles), then the tiles of Sigma
-    m = a + (long long)N * N;           // L^-1 (lower tiles; the diagonal tiles hold L_kk^-1)
-    diag = m + (long long)N * N;        // diagonal of S0 (1 on held and padding rows)
-    need = diag + N;                    // ints [T][T]: lower tile (I, J) holds a requested entry
-    hdr = need + ((long long)T * T + 1) / 2;  // [0] the parked lambda, [1] (int) status
-    total = hdr + 8;
-  }
-};
-
-__device__ __forceinline__ bool cov_free(const slam_ba_problem& p, int r) {
-  if (r >= 9 * p.n_cams) return false;
-  return p.cam_fixed == nullptr || ((p.cam_fixed[r / 9] >> (r % 9)) & 1u) == 0;
-}
-__device__ __forceinline__ bool cov_failed(const double* ws, const CovLayout& L) {
-  return *reinterpret_cast<const volatile int*>(ws + L.hdr + 1) != 0;
-}
-// lower tile (I, J), I >= J, of linear index idx = I (I + 1) / 2 + J
-__device__ __forceinline__ int2 cov_tile_of(int idx) {
-  int I = (int)((sqrtf(8.0f * (float)idx + 1.0f) - 1.0f) * 0.5f);
-  while ((I + 1) * (I + 2) / 2 <= idx) ++I;
-  while (I * (I + 1) / 2 > idx) --I;
-  return int2{I, idx - I * (I + 1) / 2};
-}
-
-// restore == 0: lambda parked in the workspace and set to 0, status cleared;
-// restore == 1: lambda back.  No other state slot is touched.
-__global__ void k_cov_lambda(slam_ba_problem p, double* ws, int restore) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  const CovLayout L(p.n_cams);
-  if (restore) {
-    p.state[SLAM_BA_ST_LAMBDA] = ws[L.hdr];
-  } else {
-    ws[L.hdr] = p.state[SLAM_BA_ST_LAMBDA];
-    p.state[SLAM_BA_ST_LAMBDA] = 0.0;
-    *reinterpret_cast<int*>(ws + L.hdr + 1) = 0;
-  }
-}
-
-// One workgroup per lower tile: S0 from the dense sys (zeros for a packed one,
-// k_cov_scatter follows), identity on held and padding rows; the diagonal of S0.
-__global__ __launch_bounds__(kTlWG) void k_cov_load(slam_ba_problem p, double* ws) {
-  const CovLayout L(p.n_cams);
-  const int n = 9 * p.n_cams;
-  const int2 IJ = cov_tile_of(blockIdx.x);
-  const bool dense = !sys_packed(p.n_cams);
-  double* A = ws + L.a;
-  for (int e = threadIdx.x; e < kTB * kTB; e += kTlWG) {
-    const int i = IJ.x * kTB + (e >> 6), j = IJ.y * kTB + (e & 63);
-    double v = i == j ? 1.0 : 0.0;
-    if (cov_free(p, i) && cov_free(p, j)) v = dense ? p.sys[(size_t)i * n + j] : 0.0;
-    A[(size_t)i * L.N + j] = v;
-  }
-  if (IJ.x == IJ.y && threadIdx.x < kTB) {
-    const int i = IJ.x * kTB + threadIdx.x;
-    if (!cov_free(p, i)) ws[L.diag + i] = 1.0;
-    else if (dense) ws[L.diag + i] = p.sys[(size_t)i * n + i];
-  }
-  if (threadIdx.x == 0) reinterpret_cast<int*>(ws + L.need)[IJ.x * L.T + IJ.y] = 0;
-}
-
-// One workgroup per packed block: its free entries into the lower tiles (both
-// triangles inside a diagonal tile), the diagonal of S0.
-__global__ __launch_bounds__(128) void k_cov_scatter(slam_ba_problem p, double* ws) {
-  const CovLayout L(p.n_cams);
-  const int blk = blockIdx.x, t = threadIdx.x;
-  if (t >= 81) return;
-  const int c1 = p.blocks[2 * blk], c2 = p.blocks[2 * blk + 1];
-  const int r = 9 * c1 + t / 9, c = 9 * c2 + t % 9;
-  if (!cov_free(p, r) || !cov_free(p, c)) return;
-  const double v = p.sys[(size_t)blk * 81 + t];
-  double* A = ws + L.a;
-  const int tr = r / kTB, tc = c / kTB;
-  if (tr >= tc) A[(size_t)r * L.N + c] = v;
-  if (c1 != c2 && tc >= tr) A[(size_t)c * L.N + r] = v;
-  if (r == c) ws[L.diag + r] = v;
-}
-
-// The lower tiles that hold an entry of a requested block (a block may straddle tiles).
-__global__ __launch_bounds__(kBS) void k_cov_mark(slam_ba_problem p, const int32_t* __restrict__ pairs,
-                                                  int n_pairs, double* ws) {
-  const CovLayout L(p.n_cams);
-  const int q = blockIdx.x * kBS + threadIdx.x;
-  if (q >= n_pairs) return;
-  const int a = pairs[2 * q], b = pairs[2 * q + 1];
-  if ((unsigned)a >= (unsigned)p.n_cams || (unsigned)b >= (unsigned)p.n_cams) return;
-  int* need = reinterpret_cast<int*>(ws + L.need);
-  for (int ta = 9 * a / kTB; ta <= (9 * a + 8) / kTB; ++ta)
-    for (int tb = 9 * b / kTB; tb <= (9 * b + 8) / kTB; ++tb) need[max(ta, tb) * L.T + min(ta, tb)] = 1;
-}
-
-// Tile column k, one workgroup per tile (I, k), I = k + blockIdx.x: every one
-// factors A_kk (tile_chol_inv_blk: L_kk^-1); the diagonal one stores L_kk^-1 as
-// the diagonal tile of L^-1 and runs the relative-pivot test, the others form
-// L_Ik = A_Ik L_kk^-T in place.
-__global__ __launch_bounds__(kTlWG) __attribute__((amdgpu_waves_per_eu(1, 1)))
-void k_cov_panel(slam_ba_problem p, double* ws, int k, double rank_tol) {
-  const CovLayout L(p.n_cams);
-  const int I = k + blockIdx.x;
-  __shared__ double VX[2 * kTB * kTB];
-  double* Vf = VX;                        // L_kk^-1, fragment order
-  __shared__ double Xf[kTB * kTB];        // A_Ik, fragment order
-  __shared__ int okf;
-  // this launch's diagonal workgroup may raise the status while others start:
-  // one lane reads it for the whole workgroup
-  if (threadIdx.x == 0) okf = cov_failed(ws, L) ? 1 : 0;
-  __syncthreads();
-  if (okf != 0) return;
-  __syncthreads();  // okf is written again by the tile factor
-  double* A = ws + L.a;
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const double* Akk = A + (size_t)k * kTB * L.N + k * kTB;
-  double* AIk = A + (size_t)I * kTB * L.N + k * kTB;
-  if (I > k && w >= 2) tile_to_frag(AIk, L.N, Xf, w - 2, 2);
-  double x[kTB];
-  double* Mb = VX;
-  double* Xb = VX + kTB * kMS;
-  double* Tb = Xb + 10 * 16 * kBS17;
-  const int rows = min(kTB, 9 * p.n_cams - k * kTB);
-  const bool ok = tile_chol_inv_blk(Akk, L.N, Mb, Xb, Tb, &okf, (rows + 15) >> 4);
-  if (w == 1) {
-    const int cb16 = lane >> 4;
-#pragma unroll
-    for (int m = 0; m < kTB; ++m)
-      x[m] = (m >> 4) >= cb16 ? Xb[blk_id(m >> 4, cb16) * 16 * kBS17 + (m & 15) * kBS17 + (lane & 15)]
-                              : 0.0;
-  }
-  __syncthreads();  // VX is reused below
-  if (w == 1) {
-    if (I == k) {
-      double* Mkk = ws + L.m + (size_t)k * kTB * L.N + k * kTB;
-#pragma unroll
-      for (int m = 0; m < kTB; ++m) Mkk[(size_t)m * L.N + lane] = x[m];
-      // pivot d = L_cc^2 = 1 / (L_kk^-1)_cc^2 against rank_tol * S0_cc
-      double xd = 0.0;
-#pragma unroll
-      for (int m = 0; m < kTB; ++m) xd = m == lane ? x[m] : xd;
-      const double piv = 1.0 / (xd * xd);
-      const bool bad = !ok || !(xd > 0.0 && xd < INFINITY) || !(piv < INFINITY) ||
-                       piv <= rank_tol * ws[L.diag + k * kTB + lane];
-      if (__any(bad) && lane == 0) *reinterpret_cast<int*>(ws + L.hdr + 1) = 1;
-    } else {
-#pragma unroll
-      for (int m = 0; m < kTB; ++m) Vf[frag_idx(m, lane)] = x[m];
-    }
-  }
-  if (I == k || !ok) return;
-  __syncthreads();
-  d4 acc[4];
-  gemm_xyT_lowY(Xf, Vf, acc);  // L_Ik = A_Ik (L_kk^-1)^T
-  cov_store(AIk, L.N, acc);
-}
-
-// Trailing update of column k, one workgroup per tile (I, J), I >= J > k:
-// A_IJ -= L_Ik L_Jk^T.
-__global__ __launch_bounds__(kTlWG) void k_cov_update(slam_ba_problem p, double* ws, int k) {
-  const CovLayout L(p.n_cams);
-  if (cov_failed(ws, L)) return;
-  const int2 IJ = cov_tile_of(blockIdx.x);
-  const int I = k + 1 + IJ.x, J = k + 1 + IJ.y;
-  __shared__ double Xf[kTB * kTB], Yf[kTB * kTB];
-  double* A = ws + L.a;
-  tile_to_frag(A + (size_t)I * kTB * L.N + k * kTB, L.N, Xf);
-  if (I != J) tile_to_frag(A + (size_t)J * kTB * L.N + k * kTB, L.N, Yf);
-  __syncthreads();
-  d4 acc[4];
-#pragma unroll
-  for (int s = 0; s < 4; ++s) acc[s] = d4{0.0, 0.0, 0.0, 0.0};
-  cov_gemm(Xf, I == J ? Xf : Yf, acc);
-  cov_store(A + (size_t)I * kTB * L.N + J * kTB, L.N, acc, true);
-}
-
-// Tile row i of M = L^-1, one workgroup per tile (i, j), j < i:
-// M_ij = -L_ii^-1 sum_{k=j}^{i-1} L_ik M_kj  (rows < i of M are complete).
-__global__ __launch_bounds__(kTlWG) void k_cov_minv(slam_ba_problem p, double* ws, int i) {
-  const CovLayout L(p.n_cams);
-  if (cov_failed(ws, L)) return;
-  const int j = blockIdx.x;
-  __shared__ double Xf[kTB * kTB], Yf[kTB * kTB];
-  const double* A = ws + L.a;
-  double* M = ws + L.m;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  d4 acc[4];
-#pragma unroll
-  for (int s = 0; s < 4; ++s) acc[s] = d4{0.0, 0.0, 0.0, 0.0};
-  for (int k = j; k < i; ++k) {
-    tile_to_frag(A + (size_t)i * kTB * L.N + k * kTB, L.N, Xf);
-    tile_to_frag_t(M + (size_t)k * kTB * L.N + j * kTB, L.N, Yf);
-    __syncthreads();
-    cov_gemm(Xf, Yf, acc);
-    __syncthreads();  // Xf / Yf reloaded next k
-  }
-  tile_to_frag(M + (size_t)i * kTB * L.N + i * kTB, L.N, Xf);
-#pragma unroll
-  for (int s = 0; s < 4; ++s)
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-      Yf[frag_idx(s * 16 + (lane & 15), w * 16 + (lane >> 4) + 4 * r)] = acc[s][r];  // the sum, transposed image
-  __syncthreads();
-#pragma unroll
-  for (int s = 0; s < 4; ++s) acc[s] = d4{0.0, 0.0, 0.0, 0.0};
-  cov_gemm(Xf, Yf, acc, true);
-  cov_store(M + (size_t)i * kTB * L.N + j * kTB, L.N, acc);
-}
-
-// Sigma_IJ = sum_{k >= I} M_kI^T M_kJ for the marked lower tiles (I >= J), into
-// the tiles of the factor (dead by now).
-__global__ __launch_bounds__(kTlWG) void k_cov_sigma(slam_ba_problem p, double* ws) {
-  const CovLayout L(p.n_cams);
-  if (cov_failed(ws, L)) return;
-  const int2 IJ = cov_tile_of(blockIdx.x);
-  const int I = IJ.x, J = IJ.y;
-  if (reinterpret_cast<const int*>(ws + L.need)[I * L.T + J] == 0) return;
-  __shared__ double Xf[kTB * kTB], Yf[kTB * kTB];
-  const double* M = ws + L.m;
-  d4 acc[4];
-#pragma unroll
-  for (int s = 0; s < 4; ++s) acc[s] = d4{0.0, 0.0, 0.0, 0.0};
-  for (int k = I; k < L.T; ++k) {
-    tile_to_frag_t(M + (size_t)k * kTB * L.N + I * kTB, L.N, Xf);
-    if (I != J) tile_to_frag_t(M + (size_t)k * kTB * L.N + J * kTB, L.N, Yf);
-    __syncthreads();
-    cov_gemm(Xf, I == J ? Xf : Yf, acc);
-    __syncthreads();
-  }
-  cov_store(ws + L.a + (size_t)I * kTB * L.N + J * kTB, L.N, acc);
-}
-
-// One workgroup per requested block: entry (i, j) from the lower triangle of
-// Sigma (so a marginal block is exactly symmetric and block (a, b) is block
-// (b, a) transposed bit for bit), +0.0 on held rows and columns, NaN when the
-// system was not positive definite; the status.
-__global__ __launch_bounds__(128) void k_cov_pick(slam_ba_problem p, const int32_t* __restrict__ pairs,
-                                                  const double* __restrict__ ws, double* __restrict__ cov,
-                                                  int32_t* __restrict__ status) {
-  const CovLayout L(p.n_cams);
-  const bool failed = cov_failed(ws, L);
-  const int q = blockIdx.x, t = threadIdx.x;
-  if (q == 0 && t == 0) status[0] = failed ? 1 : 0;
-  if (t >= 81) return;
-  const int a = pairs[2 * q], b = pairs[2 * q + 1];
-  double v = __builtin_nan("");
-  if (!failed && (unsigned)a < (unsigned)p.n_cams && (unsigned)b < (unsigned)p.n_cams) {
-    const int i = 9 * a + t / 9, j = 9 * b + t % 9;
-    v = 0.0;
-    if (cov_free(p, i) && cov_free(p, j)) v = ws[L.a + (size_t)max(i, j) * L.N + min(i, j)];
-  }
-  cov[(size_t)q * 81 + t] = v;
-}
-
-// ---------------------------------------------------------------- landmark covariance
-// Point blocks Sigma_pp and point-camera blocks Sigma_pc of the same inverse
-// (DESIGN.md 4c), from Sigma_cc as k_cov_sigma left it: per observation o of a
-// point, J~ = (Jc | Jp) as k_linearize forms it, and
-//   Sigma_pp = V^-1 + V^-1 (sum_{o,o'} Jp_o^T (Jc_o Sigma_{c(o)c(o')} Jc_o'^T) Jp_o') V^-1,
-//   Sigma_pc = -V^-1 sum_o Jp_o^T (Jc_o Sigma_{c(o),c}),      V = sum_o Jp_o^T Jp_o
-// (W_o^T Sigma W_o' with W = Jc^T Jp, the 2 x 2 middle factor formed first:
-// 24 staged doubles per observation instead of 33, 230 multiplies per pair
-// instead of 324).  One wave per requested entry, kCovPW entries per
-// workgroup; the waves never meet (no __syncthreads), sums are fixed shuffle
-// trees, so an entry's bits do not depend on the request around it.
-constexpr int kCovPW = 4;   // waves per workgroup
-constexpr int kCovCh = 8;   // observations per chunk: a step covers the 8 x 8 ordered pairs of two chunks
-constexpr int kCovJS = 25;  // LDS stride of a staged 2 x 12 Jacobian (odd: rows spread over the banks)
-
-__device__ __forceinline__ double cov_sig(const double* __restrict__ ws, const CovLayout& L, int i, int j) {
-  return ws[L.a + (size_t)max(i, j) * L.N + min(i, j)];
-}
-
-// J~ of observation o: the steps of k_linearize in its order
-__device__ __forceinline__ void cov_obs_jac(const slam_ba_problem& p, int cur, int o, double J[2][12]) {
-  double r[2];
-  const int c = p.obs_cam[o];
-  reproject_pre<true>(p.camrec[cur] + kCamRec * c, p.pts[cur] + 3 * p.obs_pt[o], p.obs_q + 2 * o, r, J);
-  clamp_rows<true>(r, J);
-  if (p.cam_fixed != nullptr) hold_cols(J, p.cam_fixed[c]);
-  if (p.loss != 0) robust_weight<12>(r, J[0], J[1], p.loss, p.loss_scale);
-}
-
-// the tree of block_sum over one wave; the sum on every lane
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return __shfl(v, 0, 64);
-}
-
-__device__ __forceinline__ void cov_mark_block(int* need, int T, int a, int b) {
-  for (int ta = 9 * a / kTB; ta <= (9 * a + 8) / kTB; ++ta)
-    for (int tb = 9 * b / kTB; tb <= (9 * b + 8) / kTB; ++tb) need[max(ta, tb) * T + min(ta, tb)] = 1;
-}
-
-// The lower tiles the point and cross requests read: blocks (c(o), c(o')) of a
-// requested point, (c(o), c) of a requested (point, camera).  One lane per entry.
-__global__ __launch_bounds__(kBS) void k_cov_mark_pts(slam_ba_problem p, const int32_t* __restrict__ points,
-                                                      int n_points, const int32_t* __restrict__ cross,
-                                                      int n_cross, double* ws) {
-  const CovLayout L(p.n_cams);
-  const int q = blockIdx.x * kBS + threadIdx.x;
-  if (q >= n_points + n_cross) return;
-  int* need = reinterpret_cast<int*>(ws + L.need);
-  const bool is_pt = q < n_points;
-  const int pt = is_pt ? (points ? points[q] : q) : cross[2 * (q - n_points)];
-  const int c = is_pt ? 0 : cross[2 * (q - n_points) + 1];
-  if ((unsigned)pt >= (unsigned)p.n_pts || (unsigned)c >= (unsigned)p.n_cams) return;
-  const int o0 = p.pt_ptr[pt], o1 = p.pt_ptr[pt + 1];
-  for (int o = o0; o < o1; ++o) {
-    const int a = p.obs_cam[o];
-    if (!is_pt) {
-      cov_mark_block(need, L.T, a, c);
-      continue;
-    }
-    for (int o2 = o0; o2 <= o; ++o2) cov_mark_block(need, L.T, a, p.obs_cam[o2]);  // (a, b) and (b, a): one lower tile
-  }
-}
-
-// Both status words of slam_ba_covariance_points, before the kernels that count.
-__global__ void k_cov_status(slam_ba_problem p, const double* __restrict__ ws, int32_t* __restrict__ status) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  status[0] = cov_failed(ws, CovLayout(p.n_cams)) ? 1 : 0;
-  status[1] = 0;
-}
-
-// V^-1 of point pt by a whole wave, the same on every lane: lanes over the
-// observations, the six sums by wave_sum, the pivots of the unpivoted 3x3
-// Cholesky (as squares: d_k of L D L^T) against rank_tol V_kk, the inverse by
-// cofactors.  false: the point is undetermined.
-__device__ __forceinline__ bool cov_point_vinv(const slam_ba_problem& p, int cur, int pt, double rank_tol,
-                                               double iv[6]) {
-  const int lane = threadIdx.x & 63;
-  const int o0 = p.pt_ptr[pt], o1 = p.pt_ptr[pt + 1];
-  double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int ob = o0; ob < o1; ob += 64) {
-    const int o = ob + lane;
-    if (o < o1) {
-      double J[2][12];
-      cov_obs_jac(p, cur, o, J);
-#pragma unroll
-      for (int a = 0; a < 2; ++a) {
-        v[0] += J[a][9] * J[a][9];
-        v[1] += J[a][9] * J[a][10];
-        v[2] += J[a][9] * J[a][11];
-        v[3] += J[a][10] * J[a][10];
-        v[4] += J[a][10] * J[a][11];
-        v[5] += J[a][11] * J[a][11];
-      }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 6; ++k) v[k] = wave_sum(v[k]);
-  const double a00 = v[0], a01 = v[1], a02 = v[2], a11 = v[3], a12 = v[4], a22 = v[5];
-  const double d0 = a00;
-  const double l10 = a01 / d0, l20 = a02 / d0;
-  const double d1 = a11 - l10 * a01;
-  const double u21 = a12 - l20 * a01;
-  const double d2 = a22 - l20 * a02 - (u21 / d1) * u21;
-  const double c00 = a11 * a22 - a12 * a12;
-  const double c01 = a02 * a12 - a01 * a22;
-  const double c02 = a01 * a12 - a02 * a11;
-  const double c11 = a00 * a22 - a02 * a02;
-  const double c12 = a01 * a02 - a00 * a12;
-  const double c22 = a00 * a11 - a01 * a01;
-  const double det = a00 * c00 + a01 * c01 + a02 * c02;
-  const bool ok = d0 > rank_tol * a00 && d0 < INFINITY && d1 > rank_tol * a11 && d1 < INFINITY &&
-                  d2 > rank_tol * a22 && d2 < INFINITY && det > 0.0 && det < INFINITY;  // (a NaN fails every test)
-  const double id = 1.0 / det;
-  iv[0] = c00 * id; iv[1] = c01 * id; iv[2] = c02 * id;
-  iv[3] = c11 * id; iv[4] = c12 * id; iv[5] = c22 * id;
-  return ok;
-}
-
-// Sigma_pp of the requested points, [n_points][3][3].  A wave walks the pairs of
-// 8-observation chunks (A, B) of its point: lanes 0..15 stage the J~ of the two
-// chunks in LDS (recomputed per step: nothing of the point is kept beyond 16
-// rows, so a deep point needs no more LDS than a shallow one), lane (a, b)
-// adds observation pair (8A + a, 8B + b) to its six entries.
-__global__ __launch_bounds__(64 * kCovPW) void k_cov_points(slam_ba_problem p, const int32_t* __restrict__ points,
-                                                            int n_points, double rank_tol,
-                                                            const double* __restrict__ ws,
-                                                            double* __restrict__ cov_pp,
-                                                            int32_t* __restrict__ status) {
-  __shared__ double Js[kCovPW][2 * kCovCh][kCovJS];
-  __shared__ int Cs[kCovPW][2 * kCovCh];
-  const CovLayout L(p.n_cams);
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int q = blockIdx.x * kCovPW + w;
-  if (q >= n_points) return;
-  const int pt = points ? points[q] : q;
-  double* out = cov_pp + (size_t)q * 9;
-  if (cov_failed(ws, L) || (unsigned)pt >= (unsigned)p.n_pts) {
-    if (lane < 9) out[lane] = __builtin_nan("");
-    return;
-  }
-  const int cur = cur_of(p.state);
-  double iv[6];
-  if (!cov_point_vinv(p, cur, pt, rank_tol, iv)) {
-    if (lane < 9) out[lane] = __builtin_nan("");
-    if (lane == 0) atomicAdd(status + 1, 1);
-    return;
-  }
-  const int o0 = p.pt_ptr[pt], n = p.pt_ptr[pt + 1] - o0;
-  const int nch = (n + kCovCh - 1) / kCovCh;
-  const int a = lane >> 3, b = lane & 7;
-  double m[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  for (int A = 0; A < nch; ++A)
-    for (int B = 0; B < nch; ++B) {
-      if (lane < 2 * kCovCh) {
-        const int k = (lane < kCovCh ? A : B) * kCovCh + (lane & (kCovCh - 1));
-        if (k < n) {
-          double J[2][12];
-          cov_obs_jac(p, cur, o0 + k, J);
-#pragma unroll
-          for (int r = 0; r < 2; ++r)
-#pragma unroll
-            for (int i = 0; i < 12; ++i) Js[w][lane][12 * r + i] = J[r][i];
-          Cs[w][lane] = p.obs_cam[o0 + k];
-        }
-      }
-      wave_lds_fence();
-      if (A * kCovCh + a < n && B * kCovCh + b < n) {
-        const double* Ja = Js[w][a];
-        const double* Jb = Js[w][kCovCh + b];
-        const int ia = 9 * Cs[w][a], ib = 9 * Cs[w][kCovCh + b];
-        double g00 = 0.0, g01 = 0.0, g10 = 0.0, g11 = 0.0;  // Jc_a Sigma_{c(a) c(b)} Jc_b^T
-        for (int s = 0; s < 9; ++s) {
-          double t0 = 0.0, t1 = 0.0;
-#pragma unroll
-          for (int r = 0; r < 9; ++r) {
-            const double sg = cov_sig(ws, L, ia + r, ib + s);
-            t0 += Ja[r] * sg;
-            t1 += Ja[12 + r] * sg;
-          }
-          g00 += t0 * Jb[s];
-          g01 += t0 * Jb[12 + s];
-          g10 += t1 * Jb[s];
-          g11 += t1 * Jb[12 + s];
-        }
-        int e = 0;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-          const double h0 = Ja[9 + i] * g00 + Ja[21 + i] * g10, h1 = Ja[9 + i] * g01 + Ja[21 + i] * g11;
-#pragma unroll
-          for (int j = i; j < 3; ++j) m[e++] += h0 * Jb[9 + j] + h1 * Jb[21 + j];
-        }
-      }
-      wave_lds_fence();  // the rows are staged again in the next step
-    }
-#pragma unroll
-  for (int k = 0; k < 6; ++k) m[k] = wave_sum(m[k]);
-  if (lane != 0) return;
-  // V^-1 + V^-1 (M V^-1): six entries, mirrored
-  const double M[3][3] = {{m[0], m[1], m[2]}, {m[1], m[3], m[4]}, {m[2], m[4], m[5]}};
-  const double IV[3][3] = {{iv[0], iv[1], iv[2]}, {iv[1], iv[3], iv[4]}, {iv[2], iv[4], iv[5]}};
-  double X[3][3], S[3][3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) X[i][j] = M[i][0] * IV[0][j] + M[i][1] * IV[1][j] + M[i][2] * IV[2][j];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = i; j < 3; ++j)
-      S[i][j] = S[j][i] = IV[i][j] + (IV[i][0] * X[0][j] + IV[i][1] * X[1][j] + IV[i][2] * X[2][j]);
-#pragma unroll
-  for (int i = 0; i < 9; ++i) out[i] = S[i / 3][i % 3];
-}
-
-// Sigma_pc of the requested (point, camera) entries, [n_cross][3][9]: lanes over
-// the point's observations, 27 sums by wave_sum, then -V^-1 . ; +0.0 in the
-// columns of held parameters of the camera.
-__global__ __launch_bounds__(64 * kCovPW) void k_cov_cross(slam_ba_problem p, const int32_t* __restrict__ cross,
-                                                           int n_cross, double rank_tol,
-                                                           const double* __restrict__ ws,
-                                                           double* __restrict__ cov_pc,
-                                                           int32_t* __restrict__ status) {
-  const CovLayout L(p.n_cams);
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int q = blockIdx.x * kCovPW + w;
-  if (q >= n_cross) return;
-  const int pt = cross[2 * q], c = cross[2 * q + 1];
-  double* out = cov_pc + (size_t)q * 27;
-  if (cov_failed(ws, L) || (unsigned)pt >= (unsigned)p.n_pts || (unsigned)c >= (unsigned)p.n_cams) {
-    if (lane < 27) out[lane] = __builtin_nan("");
-    return;
-  }
-  const int cur = cur_of(p.state);
-  double iv[6];
-  if (!cov_point_vinv(p, cur, pt, rank_tol, iv)) {
-    if (lane < 27) out[lane] = __builtin_nan("");
-    if (lane == 0) atomicAdd(status + 1, 1);
-    return;
-  }
-  const int o0 = p.pt_ptr[pt], o1 = p.pt_ptr[pt + 1];
-  double acc[27];
-#pragma unroll
-  for (int k = 0; k < 27; ++k) acc[k] = 0.0;
-  for (int ob = o0; ob < o1; ob += 64) {
-    const int o = ob + lane;
-    if (o < o1) {
-      double J[2][12];
-      cov_obs_jac(p, cur, o, J);
-      const int ia = 9 * p.obs_cam[o];
-#pragma unroll
-      for (int s = 0; s < 9; ++s) {
-        double t0 = 0.0, t1 = 0.0;  // (Jc_o Sigma_{c(o), c})[:, s]
-#pragma unroll
-        for (int r = 0; r < 9; ++r) {
-          const double sg = cov_sig(ws, L, ia + r, 9 * c + s);
-          t0 += J[0][r] * sg;
-          t1 += J[1][r] * sg;
-        }
-#pragma unroll
-        for (int i = 0; i < 3; ++i) acc[9 * i + s] += J[0][9 + i] * t0 + J[1][9 + i] * t1;
-      }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 27; ++k) acc[k] = wave_sum(acc[k]);
-  if (lane != 0) return;
-  const unsigned fx = p.cam_fixed != nullptr ? p.cam_fixed[c] : 0u;
-  const double IV[3][3] = {{iv[0], iv[1], iv[2]}, {iv[1], iv[3], iv[4]}, {iv[2], iv[4], iv[5]}};
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int s = 0; s < 9; ++s) {
-      const double v = 0.0 - (IV[i][0] * acc[s] + IV[i][1] * acc[9 + s] + IV[i][2] * acc[18 + s]);  // (never -0.0)
-      out[9 * i + s] = ((fx >> s) & 1u) ? 0.0 : v;
-    }
-}
-
-}  // namespace
-
-extern "C" long long slam_ba_cov_workspace_len(int n_cams) {
-  if (n_cams <= 0) return 0;
-  return CovLayout(n_cams).total;
-}
-
-namespace {
-
-struct CovRequest {
-  const int32_t* pairs;   int n_pairs;  double* cov;      // camera blocks (k_cov_mark, k_cov_pick)
-  const int32_t* points;  int n_points; double* cov_pp;   // point blocks (null list: every point in order)
-  const int32_t* cross;   int n_cross;  double* cov_pc;   // (point, camera) blocks
-  bool two_words;                                         // d_status [2] (slam_ba_covariance_points)
-};
-
-// The launches of both covariance entry points: one build at lambda = 0, one
-// factorisation, Sigma on the marked tiles, then the requested blocks.
-int cov_launch(const Launch& La, const CovRequest& rq, double rank_tol, double* d_ws, int32_t* d_status,
-               hipStream_t s) {
-  const slam_ba_problem& p = La.b.p[0];
-  const int T = CovLayout(p.n_cams).T;
-  k_cov_lambda<<<1, 64, 0, s>>>(p, d_ws, 0);
-  SLAM_LAUNCHED("k_cov_lambda");
-  const int rc = launch_build(La, s);
-  k_cov_lambda<<<1, 64, 0, s>>>(p, d_ws, 1);  // also after a failed launch: lambda goes back
-  SLAM_LAUNCHED("k_cov_lambda");
-  if (rc) return rc;
-  k_cov_load<<<T * (T + 1) / 2, kTlWG, 0, s>>>(p, d_ws);
-  SLAM_LAUNCHED("k_cov_load");
-  if (sys_packed(p.n_cams)) {
-    k_cov_scatter<<<p.n_blocks, 128, 0, s>>>(p, d_ws);
-    SLAM_LAUNCHED("k_cov_scatter");
-  }
-  if (rq.n_pairs > 0) {
-    k_cov_mark<<<nblk(rq.n_pairs, kBS), kBS, 0, s>>>(p, rq.pairs, rq.n_pairs, d_ws);
-    SLAM_LAUNCHED("k_cov_mark");
-  }
-  if (rq.n_points + rq.n_cross > 0) {
-    k_cov_mark_pts<<<nblk(rq.n_points + rq.n_cross, kBS), kBS, 0, s>>>(p, rq.points, rq.n_points, rq.cross,
-                                                                      rq.n_cross, d_ws);
-    SLAM_LAUNCHED("k_cov_mark_pts");
-  }
-  for (int k = 0; k < T; ++k) {
-    k_cov_panel<<<T - k, kTlWG, 0, s>>>(p, d_ws, k, rank_tol);
-    SLAM_LAUNCHED("k_cov_panel");
-    const int m = T - k - 1;
-    if (m > 0) {
-      k_cov_update<<<m * (m + 1) / 2, kTlWG, 0, s>>>(p, d_ws, k);
-      SLAM_LAUNCHED("k_cov_update");
-    }
-  }
-  for (int i = 1; i < T; ++i) {
-    k_cov_minv<<<i, kTlWG, 0, s>>>(p, d_ws, i);
-    SLAM_LAUNCHED("k_cov_minv");
-  }
-  k_cov_sigma<<<T * (T + 1) / 2, kTlWG, 0, s>>>(p, d_ws);
-  SLAM_LAUNCHED("k_cov_sigma");
-  if (rq.two_words) {
-    k_cov_status<<<1, 64, 0, s>>>(p, d_ws, d_status);
-    SLAM_LAUNCHED("k_cov_status");
-  }
-  if (rq.n_pairs > 0) {
-    k_cov_pick<<<rq.n_pairs, 128, 0, s>>>(p, rq.pairs, d_ws, rq.cov, d_status);
-    SLAM_LAUNCHED("k_cov_pick");
-  }
-  if (rq.n_points > 0) {
-    k_cov_points<<<nblk(rq.n_points, kCovPW), 64 * kCovPW, 0, s>>>(p, rq.points, rq.n_points, rank_tol, d_ws,
-                                                                  rq.cov_pp, d_status);
-    SLAM_LAUNCHED("k_cov_points");
-  }
-  if (rq.n_cross > 0) {
-    k_cov_cross<<<nblk(rq.n_cross, kCovPW), 64 * kCovPW, 0, s>>>(p, rq.cross, rq.n_cross, rank_tol, d_ws,
-                                                                rq.cov_pc, d_status);
-    SLAM_LAUNCHED("k_cov_cross");
-  }
-  return SLAM_OK;
-}
-
-}  // namespace
-
-extern "C" int slam_ba_covariance(const slam_ba_problem* prob, const int32_t* d_pairs, int n_pairs,
-                                  double rank_tol, double* d_cov, double* d_ws, long long ws_len,
-                                  int32_t* d_status, void* stream) {
-  Launch La;
-  if (int rc = make_launch(prob, 1, &La)) return rc;
-  SLAM_REQUIRE(n_pairs >= 1, "slam_ba_covariance: n_pairs %d < 1", n_pairs);
-  SLAM_REQUIRE(std::isfinite(rank_tol) && rank_tol >= 0.0 && rank_tol < 1.0,
-               "slam_ba_covariance: rank_tol %g must be finite and in [0, 1)", rank_tol);
-  SLAM_REQUIRE(d_pairs && d_cov && d_status, "slam_ba_covariance: null pointer");
-  const CovLayout L(prob->n_cams);
-  SLAM_REQUIRE(d_ws != nullptr && ws_len >= L.total,
-               "slam_ba_covariance: workspace of %lld doubles, slam_ba_cov_workspace_len gives %lld",
-               d_ws ? ws_len : 0ll, L.total);
-  const CovRequest rq{d_pairs, n_pairs, d_cov, nullptr, 0, nullptr, nullptr, 0, nullptr, false};
-  return cov_launch(La, rq, rank_tol, d_ws, d_status, slam::as_stream(stream));
-}
-
-extern "C" int slam_ba_covariance_points(const slam_ba_problem* prob, const int32_t* d_pairs, int n_pairs,
-                                         double* d_cov, const int32_t* d_points, int n_points,
-                                         double* d_cov_pp, const int32_t* d_cross, int n_cross,
-                                         double* d_cov_pc, double rank_tol, double* d_ws, long long ws_len,
-                                         int32_t* d_status, void* stream) {
-  Launch La;
-  if (int rc = make_launch(prob, 1, &La)) return rc;
-  SLAM_REQUIRE(n_pairs >= 0 && n_points >= 0 && n_cross >= 0,
-               "slam_ba_covariance_points: negative count (n_pairs %d, n_points %d, n_cross %d)", n_pairs,
-               n_points, n_cross);
-  SLAM_REQUIRE(n_pairs + (long long)n_points + n_cross >= 1, "slam_ba_covariance_points: nothing requested");
-  SLAM_REQUIRE(std::isfinite(rank_tol) && rank_tol >= 0.0 && rank_tol < 1.0,
-               "slam_ba_covariance_points: rank_tol %g must be finite and in [0, 1)", rank_tol);
-  SLAM_REQUIRE(d_status != nullptr && (n_pairs == 0 || (d_pairs && d_cov)) &&
-                   (n_points == 0 || (d_cov_pp && (d_points || n_points == prob->n_pts))) &&
-                   (n_cross == 0 || (d_cross && d_cov_pc)),
-               "slam_ba_covariance_points: null pointer (a null d_points needs n_points == n_pts = %d)",
-               prob->n_pts);
-  const CovLayout L(prob->n_cams);
-  SLAM_REQUIRE(d_ws != nullptr && ws_len >= L.total,
-               "slam_ba_covariance_points: workspace of %lld doubles, slam_ba_cov_workspace_len gives %lld",
-               d_ws ? ws_len : 0ll, L.total);
-  const CovRequest rq{d_pairs, n_pairs, d_cov, d_points, n_points, d_cov_pp, d_cross, n_cross, d_cov_pc, true};
-  return cov_launch(La, rq, rank_tol, d_ws, d_status, slam::as_stream(stream));
-}
-
 #ifdef SLAM_LINM_PROFILE
 extern "C" int slam_linm_stamps(unsigned long long* out, int n) {
   SLAM_HIP(hipDeviceSynchronize());
   SLAM_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_linm_stamp), (size_t)n * 8 * sizeof(unsigned long long)));
-  return SLAM_OK;
-}
-#endif
-
-#ifdef SLAM_FLOW_PROFILE
-extern "C" int slam_flow_epi_stamps(unsigned long long* out4) {
-  SLAM_HIP(hipDeviceSynchronize());
-  SLAM_HIP(hipMemcpyFromSymbol(out4, HIP_SYMBOL(g_flow_epi), 4 * sizeof(unsigned long long)));
-  return SLAM_OK;
-}
-extern "C" int slam_flow_sub_stamps(unsigned long long* out, int n_cols) {
-  SLAM_HIP(hipDeviceSynchronize());
-  SLAM_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_flow_sub), (size_t)n_cols * 8 * sizeof(unsigned long long)));
-  return SLAM_OK;
-}
-extern "C" int slam_flow_fac_stamps(unsigned long long* out16) {
-  SLAM_HIP(hipDeviceSynchronize());
-  SLAM_HIP(hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_flow_fac), 16 * sizeof(unsigned long long)));
-  return SLAM_OK;
-}
-extern "C" int slam_flow_stamps(unsigned long long* out, int n_cols) {
-  SLAM_HIP(hipDeviceSynchronize());
-  SLAM_HIP(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_flow_stamp), (size_t)n_cols * 8 * sizeof(unsigned long long)));
   return SLAM_OK;
 }
 #endif

@@ -1,6 +1,6 @@
 // What the BA translation units share: the batch descriptor, the solver-side
-// constants and reductions, the layout of sys, and the host functions through
-// which ba.hip reaches another file's launches.
+// constants and reductions, the sc1 / ticket hand-off, the layout of sys, and
+// the host functions through which one BA file reaches another's launches.
 #pragma once
 
 #include "common.hpp"
@@ -66,6 +66,25 @@ __host__ __device__ __forceinline__ long long sys_vec_off(int n_cams, int n_bloc
 }
 constexpr int kLdsMaxN = kDenseMaxN;  // k_solve_blk keeps the system in LDS up to 9C = 120
 
+// Cross-workgroup hand-off inside one launch (ticket pattern): the partials
+// are stored and loaded with agent-scope relaxed atomics, i.e. write-through
+// `sc1` stores and `sc1` loads that bypass the per-XCD L2, so no L2-wide
+// release/acquire fence is needed (MI355X_MICROARCH.md, correctness table).
+__device__ __forceinline__ void st_sc1(double* p, double v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ double ld_sc1(const double* p) {
+  return __hip_atomic_load(const_cast<double*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ unsigned ticket_add(uint32_t* p) {
+  return __hip_atomic_fetch_add(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void ticket_reset(uint32_t* p) {
+  __hip_atomic_store(p, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+constexpr int kBS = 256;   // block size of the element-wise kernels
+
 }  // namespace
 
 // Host functions that cross the BA files.  Kernels stay private to their file
@@ -85,5 +104,8 @@ struct Launch {
 
 size_t solve_blk_lds(int n_cams);                      // ba_solve.hip: LDS bytes of k_solve_blk
 int launch_solve_blk(const Launch& L, hipStream_t s);  // ba_solve.hip
+int launch_solve_tiled(const slam_ba_problem& p, hipStream_t s);  // ba_tiled.hip: k_tl3_flow or k_tl2_*
+int make_launch(const slam_ba_problem* probs, int n, Launch* L);  // ba.hip (ba_cov.hip builds through it)
+int launch_build(const Launch& L, hipStream_t s);                 // ba.hip: lineariser + k_assemble
 
 }  // namespace slam

@@ -1,5 +1,5 @@
 // The epilogue of every camera solve (k_solve_blk in ba_solve.hip,
-// k_tl2_epilogue and k_tl3_flow in ba.hip).
+// k_tl2_epilogue and k_tl3_flow in ba_tiled.hip).
 #pragma once
 
 #include "ba_common.hpp"
@@ -17,7 +17,7 @@ struct EpiSrc {
 #ifdef SLAM_FLOW_PROFILE
 // the dataflow solve's epilogue: start, x staged, pc / cost reduced, cameras prepared
 // (no relocatable device code: every file that includes this header has its
-// own copy.  Only the GLOBAL epilogue stamps it, and only ba.hip instantiates
+// own copy.  Only the GLOBAL epilogue stamps it, and only ba_tiled.hip instantiates
 // that one, so its slam_flow_epi_stamps reads the copy that k_tl3_flow /
 // k_tl2_epilogue write.)
 __device__ unsigned long long g_flow_epi[4];

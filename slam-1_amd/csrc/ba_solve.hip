@@ -1,5 +1,5 @@
 // BA, the one-workgroup camera solve k_solve_blk (9C <= kLdsMaxN: the local-BA
-// window; larger systems: the tiled solves in ba.hip).
+// window; larger systems: the tiled solves in ba_tiled.hip).
 #include "ba_common.hpp"
 #include "ba_epilogue.hpp"
 #include "dpp_fmac.hpp"

@@ -43,6 +43,9 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
 
 constexpr int kWave = 64;  // gfx950 wavefront
 
+// workgroups of bs lanes that cover n
+inline int nblk(int n, int bs) { return (n + bs - 1) / bs; }
+
 // Compile-time loop: f(std::integral_constant<int, i>) for i in [B, E).
 template <int B, int E, typename F>
 __device__ __forceinline__ void static_for(F&& f) {

@@ -86,6 +86,22 @@ __device__ __forceinline__ bool pg_failed(const double* ws, const PgLayout& L) {
   return *reinterpret_cast<const volatile int*>(ws + L.flag) != 0;
 }
 
+// The stored tiles of the row profile as the tile steps of tile_f64.hpp address
+// them: row I keeps its tiles first[I] .. I packed from tile index rowoff[I].
+// ld is an int on purpose (the steps take a row offset's type from it): with
+// 64-bit row offsets k_pg_back waits after every load of its row loop and a
+// full-profile iteration takes 5.6 ms instead of 3.5 (profiles/tile_steps/).
+struct SkylineTiles {
+  double* tiles;
+  const int32_t *first, *rowoff;
+  static constexpr int ld = kTB;
+  __device__ __forceinline__ SkylineTiles(const slam_pg_problem& p, const PgSched& S, const PgLayout& L)
+      : tiles(p.ws + L.tiles), first(p.sched + S.first), rowoff(p.sched + S.rowoff) {}
+  __device__ __forceinline__ double* at(int I, int J) const {
+    return tiles + (long long)(rowoff[I] + J - first[I]) * kTB * kTB;
+  }
+};
+
 // ---------------------------------------------------------------- SO(3)
 // a = sin(th)/th, b = (1 - cos th)/th^2, c = (th - sin th)/th^3 from th^2
 __device__ __forceinline__ void so3_abc(double t2, double& a, double& b, double& c) {
@@ -455,62 +471,12 @@ void k_pg_panel(PgArgs a, int k) {
   const slam_pg_problem& p = a.p;
   const PgSched S(p.n_poses, p.n_edges, a.T, a.P);
   const PgLayout L(p.n_poses, p.n_edges, a.T, a.n_tiles);
-  __shared__ double VX[2 * kTB * kTB];
-  double* Vf = VX;                  // L_kk^-1, fragment order
-  __shared__ double Xf[kTB * kTB];  // A_Ik, fragment order
-  __shared__ int okf;
-  // this launch's diagonal workgroup may raise the flag while others start:
-  // one lane reads it for the whole workgroup (a wave that left alone would
-  // leave the others waiting inside the tile factor)
-  if (threadIdx.x == 0) okf = pg_failed(p.ws, L) ? 1 : 0;
-  __syncthreads();
-  if (okf != 0) return;
-  __syncthreads();  // okf is written again by the tile factor
-  const int32_t* first = p.sched + S.first;
-  const int32_t* rowoff = p.sched + S.rowoff;
   const int I = blockIdx.x == 0 ? k : p.sched[S.lists + p.sched[S.col_ptr + k] + blockIdx.x - 1];
-  double* tiles = p.ws + L.tiles;
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const double* Akk = tiles + (long long)(rowoff[k] + k - first[k]) * kTB * kTB;
-  double* AIk = tiles + (long long)(rowoff[I] + k - first[I]) * kTB * kTB;
-  if (I > k && w >= 2) tile_to_frag(AIk, kTB, Xf, w - 2, 2);
-  double x[kTB];
-  double* Mb = VX;
-  double* Xb = VX + kTB * kMS;
-  double* Tb = Xb + 10 * 16 * kBS17;
   const int rows = 6 * min(kPgTP, p.n_poses - kPgTP * k);
-  const bool ok = tile_chol_inv_blk(Akk, kTB, Mb, Xb, Tb, &okf, (rows + 15) >> 4);
-  if (w == 1) {
-    const int cb16 = lane >> 4;
-#pragma unroll
-    for (int m = 0; m < kTB; ++m)
-      x[m] = (m >> 4) >= cb16 ? Xb[blk_id(m >> 4, cb16) * 16 * kBS17 + (m & 15) * kBS17 + (lane & 15)]
-                              : 0.0;
-  }
-  __syncthreads();  // VX is reused below
-  if (w == 1) {
-    if (I == k) {
-      const double bc = p.ws[L.b + k * kTB + lane];
-      double* Vkk = p.ws + L.dinv + (long long)k * kTB * kTB;
-#pragma unroll
-      for (int m = 0; m < kTB; ++m) Vkk[m * kTB + lane] = x[m];
-#pragma unroll
-      for (int m = 0; m < kTB; ++m) Vf[m * kTB + lane] = x[m] * bc;
-      wave_lds_fence();
-      double y = 0.0;
-      for (int c = 0; c < kTB; ++c) y += Vf[lane * kTB + ((c + lane) & 63)];
-      p.ws[L.y + k * kTB + lane] = y;
-      if (!ok && lane == 0) *reinterpret_cast<int*>(p.ws + L.flag) = 1;
-    } else {
-#pragma unroll
-      for (int m = 0; m < kTB; ++m) Vf[frag_idx(m, lane)] = x[m];
-    }
-  }
-  if (I == k || !ok) return;
-  __syncthreads();
-  d4 acc[4];
-  gemm_xyT_lowY(Xf, Vf, acc);  // L_Ik = A_Ik (L_kk^-1)^T
-  cov_store(AIk, kTB, acc);
+  int* fail = reinterpret_cast<int*>(p.ws + L.flag);
+  tile_panel(SkylineTiles(p, S, L), k, I, (rows + 15) >> 4, fail,
+             PanelSolveDiag{p.ws + L.dinv + (long long)k * kTB * kTB, p.ws + L.b + k * kTB, p.ws + L.y + k * kTB,
+                            fail});
 }
 
 // Column k's update pair u = (I, J), I >= J > k: A_IJ -= L_Ik L_Jk^T, and on a
@@ -520,34 +486,9 @@ __global__ __launch_bounds__(kTlWG) void k_pg_update(PgArgs a, int k) {
   const PgSched S(p.n_poses, p.n_edges, a.T, a.P);
   const PgLayout L(p.n_poses, p.n_edges, a.T, a.n_tiles);
   if (pg_failed(p.ws, L)) return;
-  const int32_t* first = p.sched + S.first;
-  const int32_t* rowoff = p.sched + S.rowoff;
   // (the pairs follow the panel rows of all columns: header word 6 of them)
   const int32_t* up = p.sched + S.lists + p.sched[6] + 2ll * (p.sched[S.upd_ptr + k] + blockIdx.x);
-  const int I = up[0], J = up[1];
-  __shared__ double Xf[kTB * kTB], Yf[kTB * kTB];
-  __shared__ double part[4][kTB];
-  double* tiles = p.ws + L.tiles;
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const double* LIk = tiles + (long long)(rowoff[I] + k - first[I]) * kTB * kTB;
-  tile_to_frag(LIk, kTB, Xf);
-  if (I != J) tile_to_frag(tiles + (long long)(rowoff[J] + k - first[J]) * kTB * kTB, kTB, Yf);
-  double bs = 0.0;  // thread (w, lane): row lane's part [16 w, 16 w + 16) of L_Ik y_k
-  if (I == J) {
-    const double* yk = p.ws + L.y + k * kTB;
-    for (int m = 16 * w; m < 16 * w + 16; ++m) bs = __builtin_fma(LIk[lane * kTB + m], yk[m], bs);
-  }
-  __syncthreads();
-  d4 acc[4];
-#pragma unroll
-  for (int s2 = 0; s2 < 4; ++s2) acc[s2] = d4{0.0, 0.0, 0.0, 0.0};
-  cov_gemm(Xf, I == J ? Xf : Yf, acc);
-  cov_store(tiles + (long long)(rowoff[I] + J - first[I]) * kTB * kTB, kTB, acc, true);
-  if (I == J) {
-    part[w][lane] = bs;
-    __syncthreads();
-    if (t < kTB) p.ws[L.b + I * kTB + t] -= ((part[0][t] + part[1][t]) + part[2][t]) + part[3][t];
-  }
+  tile_update<true>(SkylineTiles(p, S, L), up[0], up[1], k, p.ws + L.y, p.ws + L.b);
 }
 
 // x_k = L_kk^-T (y_k - sum_I L_Ik^T x_I), I over column k's panel rows
@@ -556,30 +497,9 @@ __global__ __launch_bounds__(kTlWG) void k_pg_back(PgArgs a, int k) {
   const PgSched S(p.n_poses, p.n_edges, a.T, a.P);
   const PgLayout L(p.n_poses, p.n_edges, a.T, a.n_tiles);
   if (pg_failed(p.ws, L)) return;
-  const int32_t* first = p.sched + S.first;
-  const int32_t* rowoff = p.sched + S.rowoff;
   const int r0 = p.sched[S.col_ptr + k], r1 = p.sched[S.col_ptr + k + 1];
-  __shared__ double r[kTB];
-  __shared__ double part[4][kTB];
-  const double* tiles = p.ws + L.tiles;
-  const int t = threadIdx.x, c = t & 63, q = t >> 6;
-  double s2 = 0.0;
-  for (int u = r0; u < r1; ++u) {
-    const int I = p.sched[S.lists + u];
-    const double* LIk = tiles + (long long)(rowoff[I] + k - first[I]) * kTB * kTB;
-    const double* xI = p.ws + L.x + I * kTB;
-    for (int m = 16 * q; m < 16 * q + 16; ++m) s2 = __builtin_fma(LIk[m * kTB + c], xI[m], s2);
-  }
-  part[q][c] = s2;
-  __syncthreads();
-  if (t < kTB) r[t] = p.ws[L.y + k * kTB + t] - (((part[0][t] + part[1][t]) + part[2][t]) + part[3][t]);
-  __syncthreads();
-  const double* Vkk = p.ws + L.dinv + (long long)k * kTB * kTB;  // L_kk^-1
-  double s3 = 0.0;
-  for (int m = 16 * q; m < 16 * q + 16; ++m) s3 = __builtin_fma(Vkk[m * kTB + c], r[m], s3);
-  part[q][c] = s3;
-  __syncthreads();
-  if (t < kTB) p.ws[L.x + k * kTB + t] = ((part[0][t] + part[1][t]) + part[2][t]) + part[3][t];
+  tile_back(SkylineTiles(p, S, L), k, r1 - r0, [&](int u) { return p.sched[S.lists + r0 + u]; },
+            p.ws + L.dinv + (long long)k * kTB * kTB, p.ws + L.y, p.ws + L.x);
 }
 
 // ---------------------------------------------------------------- trial and decide
@@ -801,7 +721,7 @@ __global__ __launch_bounds__(kTlWG) void k_pg_cov_fwd(PgArgs a, double* cws, int
     tile_to_frag(Lk + (long long)J * kTB * kTB, kTB, Xf);
     tile_to_frag_t(X + (long long)J * kTB * kTB, kTB, Yf);
     __syncthreads();
-    cov_gemm(Xf, Yf, acc);
+    tile_gemm_acc(Xf, Yf, acc);
     __syncthreads();  // Xf / Yf reloaded next J
   }
   tile_to_frag(Vkk, kTB, Xf);
@@ -813,8 +733,8 @@ __global__ __launch_bounds__(kTlWG) void k_pg_cov_fwd(PgArgs a, double* cws, int
   __syncthreads();
 #pragma unroll
   for (int s = 0; s < 4; ++s) acc[s] = d4{0.0, 0.0, 0.0, 0.0};
-  cov_gemm(Xf, Yf, acc, true);
-  cov_store(Yk, kTB, acc);
+  tile_gemm_acc(Xf, Yf, acc, true);
+  tile_store(Yk, kTB, acc);
 }
 
 // Backward, tile row k, one workgroup per requested column (its lowest row >
@@ -848,7 +768,7 @@ __global__ __launch_bounds__(kTlWG) void k_pg_cov_bwd(PgArgs a, double* cws, int
     tile_to_frag_t(tiles + (long long)(rowoff[I] + k - first[I]) * kTB * kTB, kTB, Xf);
     tile_to_frag_t(X + (long long)I * kTB * kTB, kTB, Yf);
     __syncthreads();
-    cov_gemm(Xf, Yf, acc);
+    tile_gemm_acc(Xf, Yf, acc);
     __syncthreads();  // Xf / Yf reloaded next I
   }
   tile_to_frag_t(p.ws + L.dinv + (long long)k * kTB * kTB, kTB, Xf);
@@ -863,8 +783,8 @@ __global__ __launch_bounds__(kTlWG) void k_pg_cov_bwd(PgArgs a, double* cws, int
   __syncthreads();  // (every read of Y_k is done before the stores below)
 #pragma unroll
   for (int s = 0; s < 4; ++s) acc[s] = d4{0.0, 0.0, 0.0, 0.0};
-  cov_gemm(Xf, Yf, acc);
-  cov_store(Xk, kTB, acc);
+  tile_gemm_acc(Xf, Yf, acc);
+  tile_store(Xk, kTB, acc);
 }
 
 // Where Cov(a, b) lies: entry (m, n) = base[m * sr + n * sc], read from the
@@ -1089,8 +1009,6 @@ __global__ __launch_bounds__(kPgWG) void k_pg_gate(PgArgs a, const int32_t* __re
 }
 
 // ---------------------------------------------------------------- host
-inline int nblk(int n, int bs) { return (n + bs - 1) / bs; }
-
 // the edge list and the buffers every entry point reads
 int pg_check_edges(const slam_pg_problem* p) {
   SLAM_REQUIRE(p != nullptr, "slam_pg: null problem");

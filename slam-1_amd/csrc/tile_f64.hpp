@@ -1,9 +1,14 @@
 // The 64x64 f64 tile operations shared by the tiled solvers: the tiled BA solve
-// and the camera covariance (ba.hip) and the pose graph's skyline factor
-// (posegraph_se3.hip).  Fragment-ordered LDS images of a tile as MFMA operands,
-// the tile products on v_mfma_f64_16x16x4_f64, and the factor + inverse of a
-// diagonal tile (tile_chol_inv_blk).  Every function is inlined into its
-// kernel; nothing here is a kernel or has storage outside SLAM_FLOW_PROFILE.
+// (ba_tiled.hip), the camera covariance (ba_cov.hip) and the pose graph's
+// skyline factor (posegraph_se3.hip).  Fragment-ordered LDS images of a tile as
+// MFMA operands, the tile products on v_mfma_f64_16x16x4_f64, the factor +
+// inverse of a diagonal tile (tile_chol_inv_blk), and the three steps of a
+// tiled solve written once (tile_panel, tile_update, tile_back, at the end).
+// Every function is inlined into its kernel and nothing here is a kernel.  The
+// three steps declare their own LDS (__shared__: tile_panel 96 KB + a flag,
+// tile_update 64 KB and 2 KB with a right-hand side, tile_back 2.5 KB), so a
+// kernel that calls one has that much LDS; nothing else has storage outside
+// SLAM_FLOW_PROFILE.
 #pragma once
 
 #include "ba_common.hpp"
@@ -369,7 +374,7 @@ __device__ __forceinline__ void tile_to_frag_t(const double* __restrict__ g, int
 }
 
 // acc[s] (wave w) += rows 16w.., cols 16s.. of the product of two fragment images
-__device__ __forceinline__ void cov_gemm(const double* Xf, const double* Yf, d4 acc[4], bool neg = false) {
+__device__ __forceinline__ void tile_gemm_acc(const double* Xf, const double* Yf, d4 acc[4], bool neg = false) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll 4
   for (int kk = 0; kk < 16; ++kk) {
@@ -380,7 +385,7 @@ __device__ __forceinline__ void cov_gemm(const double* Xf, const double* Yf, d4 
       acc[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Yf[((s * 16 + kk) << 6) + lane], acc[s], 0, 0, 0);
   }
 }
-__device__ __forceinline__ void cov_store(double* C, int ld, const d4 acc[4], bool sub = false) {
+__device__ __forceinline__ void tile_store(double* C, int ld, const d4 acc[4], bool sub = false) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
   for (int s = 0; s < 4; ++s)
@@ -389,6 +394,187 @@ __device__ __forceinline__ void cov_store(double* C, int ld, const d4 acc[4], bo
       double* c = C + (size_t)(w * 16 + (lane >> 4) + 4 * r) * ld + s * 16 + (lane & 15);
       *c = sub ? *c - acc[s][r] : acc[s][r];
     }
+}
+
+// lower tile (I, J), I >= J, of linear index idx = I (I + 1) / 2 + J
+__device__ __forceinline__ int2 lower_tile_of(int idx) {
+  int I = (int)((sqrtf(8.0f * (float)idx + 1.0f) - 1.0f) * 0.5f);
+  while ((I + 1) * (I + 2) / 2 <= idx) ++I;
+  while (I * (I + 1) / 2 > idx) --I;
+  return int2{I, idx - I * (I + 1) / 2};
+}
+
+// ---------------------------------------------------------------- the steps of a tiled solve
+// Panel, trailing update and back substitution of a blocked Cholesky over 64x64
+// tiles, once for the three solvers (the level-scheduled camera solve, the
+// camera covariance, the pose graph's skyline factor).  A solver says where its
+// tiles are through a struct with
+//   double* at(int I, int J)   first element of lower tile (I, J)
+//   ld                         its row stride; its type is the type of a row offset
+//                              (size_t in the dense layouts, int in the skyline: with
+//                              the other width the compiler waits after every load of
+//                              tile_back's row loop, profiles/tile_steps/)
+// and passes what only it does as a callable.  Lower tiles (I, J) of a dense
+// row-major N x N matrix:
+struct DenseTiles {
+  double* a;
+  size_t ld;
+  __device__ __forceinline__ DenseTiles(double* a_, int n) : a(a_), ld((size_t)n) {}
+  __device__ __forceinline__ double* at(int I, int J) const { return a + (size_t)I * kTB * ld + J * kTB; }
+};
+
+// Panel step of column k by the workgroup of tile (I, k), I >= k; all four
+// waves call it.  Every workgroup factors A_kk (L_kk^-1, tile_chol_inv_blk; nb
+// as there); the diagonal one (I == k) then runs diag(x, ok, lane, Vf) on wave
+// 1 -- x[m] = (L_kk^-1)[m][lane], ok the factor's verdict, Vf 2 * 64 * 64
+// doubles of LDS that are the wave's alone -- and the others form L_Ik = A_Ik
+// L_kk^-T in place.  *fail != 0: a factor before this one failed, nothing is
+// done.  This launch's diagonal workgroup may raise the flag while the others
+// start, so one lane reads it for the whole workgroup (a wave that left alone
+// would leave the others waiting inside the tile factor).
+template <class Tiles, class Diag>
+__device__ __forceinline__ void tile_panel(const Tiles& A, int k, int I, int nb, const int* fail, Diag diag) {
+  __shared__ double VX[2 * kTB * kTB];
+  double* Vf = VX;                        // L_kk^-1, fragment order
+  __shared__ double Xf[kTB * kTB];        // A_Ik, fragment order
+  __shared__ int okf;
+  if (threadIdx.x == 0) okf = *reinterpret_cast<const volatile int*>(fail) != 0 ? 1 : 0;
+  __syncthreads();
+  if (okf != 0) return;
+  __syncthreads();  // okf is written again by the tile factor
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  double* AIk = A.at(I, k);
+  if (I > k && w >= 2) tile_to_frag(AIk, (int)A.ld, Xf, w - 2, 2);
+  double x[kTB];
+  double* Mb = VX;
+  double* Xb = VX + kTB * kMS;
+  double* Tb = Xb + 10 * 16 * kBS17;
+  const bool ok = tile_chol_inv_blk(A.at(k, k), (int)A.ld, Mb, Xb, Tb, &okf, nb);
+  if (w == 1) {
+    const int cb16 = lane >> 4;
+#pragma unroll
+    for (int m = 0; m < kTB; ++m)
+      x[m] = (m >> 4) >= cb16 ? Xb[blk_id(m >> 4, cb16) * 16 * kBS17 + (m & 15) * kBS17 + (lane & 15)]
+                              : 0.0;
+  }
+  __syncthreads();  // VX is reused below
+  if (w == 1) {
+    if (I == k) {
+      diag(x, ok, lane, Vf);
+    } else {
+#pragma unroll
+      for (int m = 0; m < kTB; ++m) Vf[frag_idx(m, lane)] = x[m];
+    }
+  }
+  if (I == k || !ok) return;
+  __syncthreads();
+  d4 acc[4];
+  gemm_xyT_lowY(Xf, Vf, acc);  // L_Ik = A_Ik (L_kk^-1)^T
+  tile_store(AIk, (int)A.ld, acc);
+}
+
+// The diagonal workgroup of a solve's panel (tile_panel's diag): L_kk^-1 stored
+// row-major into dinv, y_k = L_kk^-1 b_k (row lane's products through LDS,
+// summed over rotated columns: no bank conflicts), the flag raised on a failed
+// factor.
+struct PanelSolveDiag {
+  double* dinv;     // L_kk^-1 [64][64]
+  const double* b;  // b_k
+  double* y;        // y_k
+  int* fail;
+  __device__ __forceinline__ void operator()(const double (&x)[kTB], bool ok, int lane, double* Vf) const {
+    const double bc = b[lane];
+#pragma unroll
+    for (int m = 0; m < kTB; ++m) dinv[m * kTB + lane] = x[m];
+#pragma unroll
+    for (int m = 0; m < kTB; ++m) Vf[m * kTB + lane] = x[m] * bc;
+    wave_lds_fence();
+    double yl = 0.0;
+    for (int c = 0; c < kTB; ++c) yl += Vf[lane * kTB + ((c + lane) & 63)];
+    y[lane] = yl;
+    if (!ok && lane == 0) *fail = 1;
+  }
+};
+
+// Trailing update of tile (I, J), I >= J, by one workgroup: A_IJ -= sum_k L_Ik
+// L_Jk^T over the source columns `cols`, on the f64 matrix cores.  cols is one
+// column (an int) or a TileCols list, taken in its order; the one-column form
+// has no loop, also not for the compiler (with a loop of one trip k_cov_update
+// took 84 registers instead of 78).  RHS: on a diagonal tile also b_I -= sum_k
+// L_Ik y_k (y, b: the whole vectors, 64 per tile) -- thread (w, lane) keeps row
+// lane's terms [16w, 16w + 16) of every column in one fma chain, the four
+// chains summed in wave order.
+struct TileCols {
+  const int32_t* k;
+  int n;
+};
+template <bool RHS, class Tiles, class Cols>
+__device__ __forceinline__ void tile_update(const Tiles& A, int I, int J, Cols cols, const double* y, double* b) {
+  __shared__ double Xf[kTB * kTB], Yf[kTB * kTB];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  d4 acc[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) acc[s] = d4{0.0, 0.0, 0.0, 0.0};
+  double bs = 0.0;
+  auto column = [&](int k) {
+    const double* LIk = A.at(I, k);
+    tile_to_frag(LIk, (int)A.ld, Xf);
+    if (I != J) tile_to_frag(A.at(J, k), (int)A.ld, Yf);
+    if constexpr (RHS) {
+      if (I == J) {
+        const double* yk = y + k * kTB;
+        for (int m = 16 * w; m < 16 * w + 16; ++m) bs = __builtin_fma(LIk[lane * A.ld + m], yk[m], bs);
+      }
+    }
+    __syncthreads();
+    tile_gemm_acc(Xf, I == J ? Xf : Yf, acc);
+  };
+  if constexpr (std::is_same_v<Cols, int>) {
+    column(cols);
+  } else {
+    for (int q = 0; q < cols.n; ++q) {
+      if (q > 0) __syncthreads();  // Xf / Yf are reloaded
+      column(cols.k[q]);
+    }
+  }
+  tile_store(A.at(I, J), (int)A.ld, acc, true);
+  if constexpr (RHS) {
+    __shared__ double part[4][kTB];
+    if (I == J) {
+      part[w][lane] = bs;
+      __syncthreads();
+      if (t < kTB) b[I * kTB + t] -= ((part[0][t] + part[1][t]) + part[2][t]) + part[3][t];
+    }
+  }
+}
+
+// Back substitution of column k by one workgroup: x_k = L_kk^-T (y_k - sum_u
+// L_Ik^T x_I) over the nr row tiles I = row(u), u ascending; dinv: L_kk^-1
+// [64][64] row-major, y and x the whole vectors.  Thread (q, c): rows [16q,
+// 16q + 16) of every product, column c, in one fma chain; the four chains
+// summed in wave order.
+template <class Tiles, class Row>
+__device__ __forceinline__ void tile_back(const Tiles& A, int k, int nr, Row row, const double* dinv,
+                                          const double* y, double* x) {
+  __shared__ double r[kTB];
+  __shared__ double part[4][kTB];
+  const int t = threadIdx.x, c = t & 63, q = t >> 6;
+  double s2 = 0.0;
+  for (int u = 0; u < nr; ++u) {
+    const int I = row(u);
+    const double* LIk = A.at(I, k);
+    const double* xI = x + I * kTB;
+    for (int m = 16 * q; m < 16 * q + 16; ++m) s2 = __builtin_fma(LIk[m * A.ld + c], xI[m], s2);
+  }
+  part[q][c] = s2;
+  __syncthreads();
+  if (t < kTB) r[t] = y[k * kTB + t] - (((part[0][t] + part[1][t]) + part[2][t]) + part[3][t]);
+  __syncthreads();
+  double s3 = 0.0;
+  for (int m = 16 * q; m < 16 * q + 16; ++m) s3 = __builtin_fma(dinv[m * kTB + c], r[m], s3);
+  part[q][c] = s3;
+  __syncthreads();
+  if (t < kTB) x[k * kTB + t] = ((part[0][t] + part[1][t]) + part[2][t]) + part[3][t];
 }
 
 }  // namespace

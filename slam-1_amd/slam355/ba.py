@@ -240,8 +240,8 @@ def upper_blocks(n_cams, cam_idx, pt_idx):
     return np.unique(np.concatenate([block_index(diag, diag, n_cams), block_index(c1, c2, n_cams)]))
 
 
-TB = 64  # tile edge of the tiled solver (csrc/ba.hip kTB)
-EPI_CAMS_MAX = 16  # cameras per tile in the dataflow solve's spread epilogue (csrc/ba.hip kEpiCams)
+TB = 64  # tile edge of the tiled solver (csrc/tile_f64.hpp kTB)
+EPI_CAMS_MAX = 16  # cameras per tile in the dataflow solve's spread epilogue (csrc/ba_tiled.hip kEpiCams)
 TILE_MODE = "rows64"  # default tiling of the camera solve (tl_schedule; measured best)
 
 
@@ -489,7 +489,7 @@ def _flow_rs_order(T, struct, level):
 
 
 def tl_schedule(n_cams, blocks, mode=None):
-    """Level schedule of the tiled camera solve (csrc/ba.hip tl_solve_levels).
+    """Level schedule of the tiled camera solve (csrc/ba_tiled.hip tl_solve_levels).
 
     The 9C-row camera system is cut into tiles (tile_rows: whole cameras by
     default, at most 64 rows each, numbered in nested-dissection order), each
@@ -504,7 +504,7 @@ def tl_schedule(n_cams, blocks, mode=None):
     panel steps.
 
     The same symbolic structure also drives the dataflow form of the solve
-    (csrc/ba.hip k_tl3_flow: one persistent workgroup per tile column, columns
+    (csrc/ba_tiled.hip k_tl3_flow: one persistent workgroup per tile column, columns
     wait for the tiles they need through device flags instead of launch
     boundaries), whose per-column table is appended.
 
@@ -1102,7 +1102,7 @@ def assembly_table(n_cams, pl):
 
 
 def tiled_solve_flops(n_cams, blocks, tb=64):
-    """Flops of the tiled Cholesky (csrc/ba.hip k_tl_*) for a packed block list
+    """Flops of the tiled Cholesky (csrc/ba_tiled.hip k_tl*) for a packed block list
     [n_blocks, 2]: the 64x64 tiles it factors, solves and updates, with the
     structural fill-in tracked as the kernels track it (zero tiles skipped)."""
     n = 9 * n_cams

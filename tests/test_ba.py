@@ -765,7 +765,7 @@ def _tiled_system(S, b, sched):
 
 
 def _emulate_tl_levels(S, b, sched):
-    """The level-scheduled tiled solve (csrc/ba.hip k_tl2_*) restated in NumPy,
+    """The level-scheduled tiled solve (csrc/ba_tiled.hip k_tl2_*) restated in NumPy,
     launch by launch: S laid out in the schedule's tiles of whole cameras, each level's
     panels (diagonal factor + inverse, y_k; L_Ik = A_Ik L_kk^-T), then its
     updates (A_IJ -= sum_k L_Ik L_Jk^T, b_I -= sum_k L_Ik y_k), then the back
@@ -888,7 +888,7 @@ def test_tl_gather_tables_lay_out_the_system(C, loop, mode):
 
 
 def _emulate_tl_flow(S, b, sched):
-    """The dataflow tiled solve (csrc/ba.hip k_tl3_flow) restated in NumPy,
+    """The dataflow tiled solve (csrc/ba_tiled.hip k_tl3_flow) restated in NumPy,
     column by column from the schedule's column table: the diagonal tile's
     updates over rs(J), its factor and inverse, y_J; each row tile's updates
     over its k list (rows 0 and 1: the product slots that the k formed
