@@ -647,6 +647,19 @@ int slam_ba_covariance_points(const slam_ba_problem* prob,
  * takes effect at the next launch (and is baked into graphs captured after). */
 int slam_ba_set_solve_lds_floor(int bytes);
 
+/* 1 (default): slam_ba_iterate / slam_ba_iterate_batch let the one-workgroup
+ * camera solve (9C <= 120) sum the lineariser's partial rows in its own
+ * workgroup, with no k_assemble launch before it, for every launch set in which
+ * no problem has asm_tab or asm_act and every problem has at most 1024 partial
+ * rows (n_cslots + n_bslots: beyond that one workgroup per window is slower
+ * than k_assemble's one per block).  2: the same without the row limit (tests,
+ * measurements).  0: the separate k_assemble launch.  sys,
+ * state and parameters are the same bits either way; slam_ba_build_system /
+ * _solve_step / _decide and the covariance calls always use k_assemble.
+ * Process-wide; read when launches are issued (a captured graph keeps what it
+ * was captured with). */
+int slam_ba_set_fused_assembly(int on);
+
 /* Minimum dynamic LDS (bytes, <= 160 KiB) k_orb_tile requests; 0 (default) =
  * what the patch needs (~79 KiB at C2: two workgroups per CU).  Between 80 and
  * ~80.6 KiB one ORB workgroup per CU leaves room for one local-BA

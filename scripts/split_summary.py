@@ -1,15 +1,16 @@
 """Per-rank split of the sharded LM iteration (scripts/gpu_r5_split3.sh output):
 rocprofv3 kernel averages of each {C4|C5}_w{W}_r{r} run -> divided (k_lin_mfma +
-k_asm_fill + k_assemble + k_back_trial) and replicated (k_tl3_flow + k_tl2_load +
-k_tl2_scatter) microseconds per LM iteration, plus the run's own wall time per
-iteration.   python scripts/split_summary.py OUTDIR > summary.json"""
+k_assemble, or the fused solve k_solve_blk<true> that assembles in its place, +
+k_back_trial) and replicated (k_tl3_flow + k_tl2_load + k_tl2_scatter)
+microseconds per LM iteration, plus the run's own wall time per iteration.   python scripts/split_summary.py OUTDIR > summary.json"""
 import csv
 import glob
 import json
 import os
 import sys
 
-DIV = ("k_lin_mfma", "k_asm_fill", "k_assemble", "k_back_trial")
+FUSED = "k_solve_blk<true>"  # assembles (no k_assemble launch) and solves: counted where k_assemble is
+DIV = ("k_lin_mfma", "k_assemble", FUSED, "k_back_trial")
 REP = ("k_tl3_flow", "k_tl2_load", "k_tl2_scatter")
 
 
@@ -21,7 +22,10 @@ def main(d):
         with open(path) as f:
             for r in csv.DictReader(f):
                 k = r["Name"].replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0]
-                k = k.split("<")[0]
+                if not k.startswith(FUSED):
+                    k = k.split("<")[0]
+                else:
+                    k = FUSED
                 if k in DIV + REP:
                     avg[k] = round(float(r["AverageNs"]) / 1e3, 1)
         e = dict(avg)

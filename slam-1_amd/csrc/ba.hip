@@ -23,6 +23,8 @@
 //   (all-reduce of sys over ranks happens here for multi-GPU)
 //   k_solve_blk     1 WG   -> damp, blocked LDL^T (MFMA trailing updates), camera  [ba_solve.hip]
 //                             step, pred_cam, trial cameras (tiled k_tl3_flow / k_tl2_* for 9C > 120)  [ba_tiled.hip]
+//                             (slam_ba_iterate_batch, windows of few partial rows: k_solve_blk<true>
+//                             sums the partials itself, in k_assemble's order, and k_assemble is not launched)
 //   k_back_trial    point group -> point step, trial points, trial |r|^2 and
 //                                  pred partials; the last group sums them into
 //                                  small (and, single rank, decides)
@@ -1513,6 +1515,16 @@ namespace {
 // pivot chain off CUs whose SIMDs are busy with ORB waves.
 static size_t g_solve_lds_floor = 0;
 
+// slam_ba_set_fused_assembly: slam_ba_iterate_batch lets the one-workgroup
+// camera solve sum the partial rows itself (k_solve_blk<true>) instead of
+// launching k_assemble before it.  Same bits either way.
+static int g_fused_assembly = 1;  // 0 never, 1 up to kFuseMaxRows partial rows per window, 2 always
+// One workgroup sums a window's rows where k_assemble spreads them over a
+// 1024-lane workgroup per block, so the fused form pays only while the rows
+// are few: the tracker's windows (16 chunks per supergroup) have ~450, a
+// window planned one chunk per supergroup ~6500 (profiles/ba_asm_solve/README.md).
+constexpr int kFuseMaxRows = 1024;
+
 static int launch_reset(const Launch& L, double lam0, hipStream_t s) {
   k_reset<<<dim3(1, L.n), 64, 0, s>>>(L.b, lam0);
   SLAM_LAUNCHED("k_reset");
@@ -1530,6 +1542,7 @@ int slam::make_launch(const slam_ba_problem* probs, int n, Launch* L) {
   L->solve_lds = 0;
   L->dense = true;
   L->robust = false;
+  L->fused = false;
   for (int i = 0; i < n; ++i) {
     if (int rc = check_problem(probs + i)) return rc;
     for (int j = 0; j < i; ++j)
@@ -1564,7 +1577,7 @@ int slam::launch_build(const Launch& L, hipStream_t s) {
     else k_linearize<false><<<dim3(L.max_grps, L.n), kLinWG, 0, s>>>(L.b);
     SLAM_LAUNCHED("k_linearize");
   }
-  if (!folded) {  // k_lin_mfma skips the fold of a problem without asm_tab
+  if (!folded && !L.fused) {  // k_lin_mfma skips the fold of a problem without asm_tab
     k_assemble<<<dim3(L.max_blocks, L.n), kAsmWG, 0, s>>>(L.b);
     SLAM_LAUNCHED("k_assemble");
   }
@@ -1592,6 +1605,12 @@ static int launch_solve(const Launch& L, bool fuse_decide, hipStream_t s) {
 extern "C" int slam_ba_set_solve_lds_floor(int bytes) {
   SLAM_REQUIRE(bytes >= 0 && bytes <= 160 * 1024, "slam_ba_set_solve_lds_floor: %d B", bytes);
   g_solve_lds_floor = (size_t)bytes;
+  return SLAM_OK;
+}
+
+extern "C" int slam_ba_set_fused_assembly(int on) {
+  SLAM_REQUIRE(on >= 0 && on <= 2, "slam_ba_set_fused_assembly: %d (0, 1 or 2)", on);
+  g_fused_assembly = on;
   return SLAM_OK;
 }
 
@@ -1654,6 +1673,14 @@ extern "C" int slam_ba_iterate_batch(const slam_ba_problem* probs, int n_probs, 
       ++n;
     Launch L;
     if (int rc = make_launch(probs + i0, n, &L)) return rc;
+    // the dense launch without folded assembly (asm_tab) or block shards
+    // (asm_act): the solve's workgroup assembles
+    L.fused = g_fused_assembly != 0 && L.dense;
+    for (int i = 0; i < n; ++i) {
+      const slam_ba_problem& q = probs[i0 + i];
+      L.fused = L.fused && q.asm_tab == nullptr && q.asm_act == nullptr &&
+                (g_fused_assembly == 2 || q.n_cslots + q.n_bslots <= kFuseMaxRows);
+    }
     for (int it = 0; it < n_iter; ++it) {
       if (int rc = launch_build(L, s)) return rc;
       if (int rc = launch_solve(L, true, s)) return rc;  // decide fused into the last group

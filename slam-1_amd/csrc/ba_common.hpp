@@ -100,12 +100,13 @@ struct Launch {
   size_t solve_lds;
   bool dense;
   bool robust;  // a problem of the batch has loss != 0: the ROBUST kernels (each branches per problem)
+  bool fused;   // the camera solve assembles (k_solve_blk<true>, no k_assemble launch): slam_ba_iterate_batch only
 };
 
 size_t solve_blk_lds(int n_cams);                      // ba_solve.hip: LDS bytes of k_solve_blk
-int launch_solve_blk(const Launch& L, hipStream_t s);  // ba_solve.hip
+int launch_solve_blk(const Launch& L, hipStream_t s);  // ba_solve.hip: k_solve_blk<L.fused>
 int launch_solve_tiled(const slam_ba_problem& p, hipStream_t s);  // ba_tiled.hip: k_tl3_flow or k_tl2_*
 int make_launch(const slam_ba_problem* probs, int n, Launch* L);  // ba.hip (ba_cov.hip builds through it)
-int launch_build(const Launch& L, hipStream_t s);                 // ba.hip: lineariser + k_assemble
+int launch_build(const Launch& L, hipStream_t s);                 // ba.hip: lineariser + k_assemble (not when L.fused)
 
 }  // namespace slam

@@ -15,7 +15,8 @@ constexpr int kSolveHdr = 32;   // doubles of LDS header in k_solve_blk
 
 // -DSLAM_SOLVE_PROFILE: phase timestamps (wall_clock64, 100 MHz) of k_solve_blk
 // into the spare LM state slots 12..15 (ns): load, eliminate, back-substitute,
-// epilogue (scripts/ba_solve_prof.py reads them).
+// epilogue, and into slot 17 the assembly prologue of k_solve_blk<true> (a part
+// of its load phase; ~0 in k_solve_blk<false>) (scripts/ba_solve_prof.py reads them).
 #ifdef SLAM_SOLVE_PROFILE
 #define SOLVE_PROF_T(i) uint64_t prof_t##i = wall_clock64()
 #define SOLVE_PROF_END()                                                        \
@@ -26,6 +27,7 @@ constexpr int kSolveHdr = 32;   // doubles of LDS header in k_solve_blk
       p.state[13] = 10.0 * (double)(prof_t2 - prof_t1);                         \
       p.state[14] = 10.0 * (double)(prof_t3 - prof_t2);                         \
       p.state[15] = 10.0 * (double)(prof_e - prof_t3);                          \
+      p.state[17] = 10.0 * (double)(prof_ta - prof_t0);                         \
     }                                                                           \
   } while (0)
 #else
@@ -108,6 +110,200 @@ __device__ unsigned long long g_solve_trace[20][6];
 #define SOLVE_TR(step, i) (void)0
 #endif
 
+// ---------------------------------------------------------------- assembly prologue
+// k_solve_blk<true> sums the window's partial rows itself, on its own 4 waves,
+// and gives what k_assemble gives bit for bit.  k_assemble's order is that of
+// rows_sum<1024, 8, false, kCPart> (ba.hip): virtual lane (part k, column e) of
+// a 1024-lane workgroup, nparts = 1024 / n, holds 8 accumulators a[u] (from
+// +0.0) over the rows rb + k + (u + 8 m) nparts, m = 0, 1, ... (its unrolled
+// trips and its remainder loop deal the rows to the accumulators alike), folds
+// them with the fixed tree pair_sum<8>, and the parts are added in order
+// k = 0, 1, ... onto +0.0.  Here one real lane walks all the parts of its
+// column in that order, so no LDS carries the parts.
+constexpr int kAsmVirt = 1024;  // k_assemble's workgroup (SLAM_ASM_WG of ba.hip)
+constexpr int kAsmNF = 8;       // its accumulators per virtual lane
+constexpr int kAsmGrp = 3;      // parts a lane walks together on the deep path (divides 9 and 12)
+
+template <int N>  // (a[0] + a[1]) + (a[2] + a[3]), ...: ba.hip's pair_sum
+__device__ __forceinline__ double asm_pair_sum(const double* a) {
+  if constexpr (N == 1) return a[0];
+  else return asm_pair_sum<N / 2>(a) + asm_pair_sum<N / 2>(a + N / 2);
+}
+
+// Column sums of the N-wide rows [rb, re) of part for the columns lane and
+// lane + 64 (the second clamped to N - 1: its spare lanes repeat the last
+// column and drop the result), in the virtual order above.  Up to HOIST rows
+// per part (all local-BA windows of the tracker) every load of both columns is
+// issued before the first add; the rows a part does not have enter as +0.0,
+// which changes no bit (an accumulator starts at +0.0 and so is never -0.0,
+// and x + +0.0 == x for every other x).  Deeper runs walk kAsmGrp parts at a
+// time through k_assemble's 8-deep trips.
+template <int N, int HOIST>
+__device__ __forceinline__ void virt_rows_sum2(const double* __restrict__ part, int stride, int rb,
+                                               int re, int lane, double& o0, double& o1) {
+  constexpr int P = kAsmVirt / N;
+  static_assert(HOIST <= kAsmNF, "hoisted rows of a part: one accumulator each");
+  const double* q0 = part + (size_t)rb * stride + lane;
+  const double* q1 = part + (size_t)rb * stride + min(lane + 64, N - 1);
+  const int R = re - rb;  // uniform
+  double v0 = 0.0, v1 = 0.0;
+  if (R <= HOIST * P) {
+    double x0[HOIST * P], x1[HOIST * P];
+#pragma unroll
+    for (int i = 0; i < HOIST * P; ++i) {
+      x0[i] = 0.0;
+      x1[i] = 0.0;
+      if (i < R) {
+        x0[i] = q0[(size_t)i * stride];
+        x1[i] = q1[(size_t)i * stride];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < P; ++k) {
+      double a0[kAsmNF] = {}, a1[kAsmNF] = {};
+#pragma unroll
+      for (int u = 0; u < HOIST; ++u) {
+        a0[u] += x0[k + u * P];
+        a1[u] += x1[k + u * P];
+      }
+      v0 += asm_pair_sum<kAsmNF>(a0);
+      v1 += asm_pair_sum<kAsmNF>(a1);
+    }
+  } else {
+    // kAsmGrp parts at a time, trip by trip: the 8 rows of a trip of each part
+    // (k_assemble's unrolled trip; its remainder is the last, partial trip with
+    // the same deal of rows to accumulators) are loaded before they are added
+    static_assert(P % kAsmGrp == 0, "parts walked in groups");
+    const int trips = ((R + P - 1) / P + kAsmNF - 1) / kAsmNF;
+#pragma unroll 1
+    for (int k0 = 0; k0 < P; k0 += kAsmGrp) {
+      double a0[kAsmGrp][kAsmNF] = {}, a1[kAsmGrp][kAsmNF] = {};
+#pragma unroll 1
+      for (int m = 0; m < trips; ++m) {
+        double y0[kAsmGrp][kAsmNF], y1[kAsmGrp][kAsmNF];
+#pragma unroll
+        for (int g = 0; g < kAsmGrp; ++g)
+#pragma unroll
+          for (int u = 0; u < kAsmNF; ++u) {
+            const int r = k0 + g + (u + kAsmNF * m) * P;
+            y0[g][u] = 0.0;
+            y1[g][u] = 0.0;
+            if (r < R) {
+              y0[g][u] = q0[(size_t)r * stride];
+              y1[g][u] = q1[(size_t)r * stride];
+            }
+          }
+#pragma unroll
+        for (int g = 0; g < kAsmGrp; ++g)
+#pragma unroll
+          for (int u = 0; u < kAsmNF; ++u) {
+            a0[g][u] += y0[g][u];
+            a1[g][u] += y1[g][u];
+          }
+      }
+#pragma unroll
+      for (int g = 0; g < kAsmGrp; ++g) {
+        v0 += asm_pair_sum<kAsmNF>(a0[g]);
+        v1 += asm_pair_sum<kAsmNF>(a1[g]);
+      }
+    }
+  }
+  o0 = v0;
+  o1 = v1;
+}
+
+// The staged tiles (all lower 16x16 tiles, 256 doubles each, from Pn on) end
+// before Dd for every window size.
+constexpr bool asm_stage_fits() {
+  for (int c = 1; 9 * c <= kLdsMaxN; ++c) {
+    const int n = 9 * c, n16 = ((n + 1 + 15) / 16) * 16, nt = n16 / 16;
+    if (nt * (nt + 1) / 2 * 256 > n16 * (kPanelW + 2 * kWLs) + n * (n - 1) / 2) return false;
+  }
+  return true;
+}
+static_assert(asm_stage_fits(), "k_solve_blk<true>: the tile staging overruns Pn / WL / LL / LF");
+
+// What k_assemble writes into sys (dense layout: S with both mirrored entries
+// of an off-diagonal block, b, g, diag U, per-camera cost; the write-out
+// statements are its statements), one wave per block, blocks dealt round-robin
+// over the 4 waves; lane l holds elements l and 64 + l of the block's 81 (of the
+// camera row's 109).  The same values go to stg (the lower tiles, tile
+// I (I + 1) / 2 + J at 256 doubles, row-major 16 x 16) and to Eb (b, g, diag U
+// at 0, n2, 2 n2; cost at 4 n2), from which the solve continues.
+__device__ __forceinline__ void asm_prologue(const slam_ba_problem& p, double* stg, double* Eb,
+                                             int n2, int wid, int lane) {
+  const int C9 = 9 * p.n_cams;
+  double* S = p.sys;
+  double* bvec = S + sys_vec_off(p.n_cams, p.n_blocks);
+  double* gvec = bvec + C9;
+  double* diagU = gvec + C9;
+  double* costc = diagU + C9;
+  auto put = [&](int row, int col, double v) {
+    S[(size_t)row * C9 + col] = v;
+    const int I = row >> 4, J = col >> 4;
+    if (I >= J) stg[(I * (I + 1) / 2 + J) * 256 + (row & 15) * 16 + (col & 15)] = v;
+  };
+  for (int blk = wid; blk < p.n_blocks; blk += kBlkWaves) {  // uniform per wave
+    const int c1 = p.blocks[2 * blk], c2 = p.blocks[2 * blk + 1];
+    const bool diag = c1 == c2;
+    const int bb = p.blk_bslot_ptr[blk], be = p.blk_bslot_ptr[blk + 1];
+    const int t0 = lane, t1 = min(lane + 64, 80);
+    const bool has1 = lane + 64 < 81;
+    const int i0 = t0 / 9, j0 = t0 - 9 * i0, i1 = t1 / 9, j1 = t1 - 9 * i1;
+    if (!diag && be == bb) {  // a block without partial rows: -sum of nothing
+      put(9 * c1 + i0, 9 * c2 + j0, -0.0);
+      put(9 * c2 + j0, 9 * c1 + i0, -0.0);
+      if (has1) {
+        put(9 * c1 + i1, 9 * c2 + j1, -0.0);
+        put(9 * c2 + j1, 9 * c1 + i1, -0.0);
+      }
+      continue;
+    }
+    double sh0 = 0.0, sh1 = 0.0, sb0 = 0.0, sb1 = 0.0;
+    if (diag)
+      virt_rows_sum2<109, 4>(p.cpart, kCPart, p.cam_cslot_ptr[c1], p.cam_cslot_ptr[c1 + 1], lane, sh0, sh1);
+    if (!diag || be > bb) virt_rows_sum2<81, 3>(p.bpart, 81, bb, be, lane, sb0, sb1);
+    if (diag) {
+      // sb[9 j + i] of the other lanes, sh[90 + t] beside sh[81 + t]
+      const int s0 = 9 * j0 + i0, s1 = 9 * j1 + i1;
+      const double a0 = __shfl(sb0, s0 & 63, 64), b0 = __shfl(sb1, s0 & 63, 64);
+      const double a1 = __shfl(sb0, s1 & 63, 64), b1 = __shfl(sb1, s1 & 63, 64);
+      const double sbT0 = s0 < 64 ? a0 : b0, sbT1 = s1 < 64 ? a1 : b1;
+      const double shu = __shfl(sh1, (lane + 9) & 63, 64);
+      put(9 * c1 + i0, 9 * c1 + j0, sh0 - (sb0 + sbT0));
+      if (has1) put(9 * c1 + i1, 9 * c1 + j1, sh1 - (sb1 + sbT1));
+      const int e = lane + 64;
+      if (e >= 81 && e < 90) {
+        const int q = 9 * c1 + e - 81;
+        const double gv = -sh1, bv = -sh1 - shu;
+        gvec[q] = gv;
+        bvec[q] = bv;
+        Eb[n2 + q] = gv;
+        Eb[q] = bv;
+      }
+      if (e >= 99 && e < 108) {
+        diagU[9 * c1 + e - 99] = sh1;
+        Eb[2 * n2 + 9 * c1 + e - 99] = sh1;
+      }
+      if (e == 108) {
+        costc[c1] = sh1;
+        Eb[4 * n2 + c1] = sh1;
+      }
+    } else {
+      put(9 * c1 + i0, 9 * c2 + j0, -sb0);
+      put(9 * c2 + j0, 9 * c1 + i0, -sb0);
+      if (has1) {
+        put(9 * c1 + i1, 9 * c2 + j1, -sb1);
+        put(9 * c2 + j1, 9 * c1 + i1, -sb1);
+      }
+    }
+  }
+}
+
+// ASM: the workgroup first assembles its window's sys from the partial rows
+// (asm_prologue above; no k_assemble launch before it) and takes the tile
+// values and b, g, diag U, cost from LDS instead of from sys.
+template <bool ASM>
 __global__ __launch_bounds__(kBlkWG) __attribute__((amdgpu_waves_per_eu(2))) void k_solve_blk(BaBatch bat) {
   BA_PROB(bat);
   lm_wave_priority();
@@ -134,7 +330,18 @@ __global__ __launch_bounds__(kBlkWG) __attribute__((amdgpu_waves_per_eu(2))) voi
   SOLVE_TR(19, 1);
   const int n2 = (n + 1) & ~1;
   if (t == 0) *fail_p = 0;
-  for (int i = t; i < 2 * g.n16 * kWLs; i += kBlkWG) WL[i] = 0.0;  // WL and LL
+  if constexpr (!ASM)
+    for (int i = t; i < 2 * g.n16 * kWLs; i += kBlkWG) WL[i] = 0.0;  // WL and LL
+  if constexpr (ASM) {
+    // the sums go to sys (an output only: never read back here), to the tile
+    // staging in Pn..LF (dead until the first panel) and to Eb (below)
+    double* Ea = lds + g.ep;
+    asm_prologue(p, Pn, Ea, n2, wid, lane);
+    const double cv = p.cams[cur_of(p.state)][min(t, n - 1)];
+    if (t < n) Ea[3 * n2 + t] = cv;
+    __syncthreads();  // staged tiles, b, g, diag U, cameras, cost
+  }
+  SOLVE_PROF_T(a);
   // this wave's tiles: tl = wid + 4 s -> (I, J), I >= J.  All S loads are
   // issued unconditionally (clamped addresses) before any is used.
   int tI[kTileMax], tJ[kTileMax];
@@ -150,11 +357,15 @@ __global__ __launch_bounds__(kBlkWG) __attribute__((amdgpu_waves_per_eu(2))) voi
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int row = min(max(tI[s], 0) * 16 + (lane >> 4) + 4 * q, n - 1);
-      acc[s][q] = S[(size_t)row * n + col];
+      if constexpr (ASM) acc[s][q] = Pn[(tl < NL ? tl : 0) * 256 + ((lane >> 4) + 4 * q) * 16 + (lane & 15)];
+      else acc[s][q] = S[(size_t)row * n + col];
     }
   }
   double* Eb = lds + g.ep;  // prefetch: b, g, diagU, live cameras, cost partials
-  {
+  if constexpr (ASM) {
+    __syncthreads();  // the staging is dead: WL / LL may be cleared, Pn written
+    for (int i = t; i < 2 * g.n16 * kWLs; i += kBlkWG) WL[i] = 0.0;  // WL and LL
+  } else {
     const double* src[5] = {bvec, bvec + n, diagU, p.cams[cur_of(p.state)], diagU + n};
     const int len[5] = {n, n, n, n, p.n_cams};
     double v[5];  // n <= kLdsMaxN < kBlkWG: one element per thread, loads issued together
@@ -163,8 +374,8 @@ __global__ __launch_bounds__(kBlkWG) __attribute__((amdgpu_waves_per_eu(2))) voi
 #pragma unroll
     for (int a = 0; a < 5; ++a)
       if (t < len[a]) Eb[a * n2 + t] = v[a];
+    __syncthreads();  // prefetched b and diagU
   }
-  __syncthreads();  // prefetched b and diagU
 #pragma unroll
   for (int s = 0; s < kTileMax; ++s) {
     const int col = tJ[s] * 16 + (lane & 15);
@@ -376,7 +587,8 @@ __global__ __launch_bounds__(kBlkWG) __attribute__((amdgpu_waves_per_eu(2))) voi
 size_t slam::solve_blk_lds(int n_cams) { return sizeof(double) * BlkLds(9 * n_cams).total; }
 
 int slam::launch_solve_blk(const Launch& L, hipStream_t s) {
-  k_solve_blk<<<dim3(1, L.n), kBlkWG, L.solve_lds, s>>>(L.b);
+  if (L.fused) k_solve_blk<true><<<dim3(1, L.n), kBlkWG, L.solve_lds, s>>>(L.b);
+  else k_solve_blk<false><<<dim3(1, L.n), kBlkWG, L.solve_lds, s>>>(L.b);
   SLAM_LAUNCHED("k_solve_blk");
   return SLAM_OK;
 }

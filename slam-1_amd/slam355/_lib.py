@@ -132,6 +132,7 @@ SIGNATURES = {
     "slam_ba_covariance_points": [_PROB, c_p, c_int, c_p, c_p, c_int, c_p, c_p, c_int, c_p, c_double, c_p,
                                   c_longlong, c_p, c_p],
     "slam_ba_set_solve_lds_floor": [c_int],
+    "slam_ba_set_fused_assembly": [c_int],
     "slam_orb_set_lds_floor": [c_int],
     "slam_orb_set_corner_cap": [c_int],
     "slam_count_min": [c_p, c_int, c_p, c_p],

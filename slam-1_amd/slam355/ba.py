@@ -1157,7 +1157,9 @@ class BAProblem:
         stream and CU mask), "levels" one launch pair per elimination-tree level;
         tile_mode: the tiling of that solve (tile_rows; default TILE_MODE).
         active_blocks (packed systems): k_assemble only over the blocks with
-        partial rows here (a landmark shard), a fill launch for the rest.
+        partial rows here (a landmark shard); those workgroups also write the
+        zeros of the other blocks and of the cameras without rows (no
+        separate launch).
         fold_assembly (lin_mode mfma): k_lin_mfma's last supergroup per camera
         block sums the block's partial rows into the system (no k_assemble
         launch).  Off by default: measured slower (the workgroup that finishes
