@@ -267,6 +267,90 @@ int slam_map_windows(double* d_maps, int32_t* d_M, int map_cap, int n_win, int n
                      void* d_ws, size_t ws_size, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Guided matching (search by projection): landmarks with descriptors are
+ * projected into a frame with its predicted pose, each is compared only with
+ * the keypoints inside a window round its predicted pixel, every keypoint goes
+ * to at most one landmark, and the matches come out as track rows.  Five
+ * steps, each asynchronous on `stream`, none allocating or synchronising.
+ *
+ * 1. Projection.  d_X [x_items][x_cap][3] f64 world points, x_items = batch, or
+ *    1 when x_shared != 0 (one map, many frames); d_nx [batch] i32 (clamped to
+ *    [0, x_cap]); d_poses [batch][16] f64 row-major camera-to-world, rigid (the
+ *    d_poses of slam_rel_to_abs; R = its 3x3, t = its last column); d_P [12]
+ *    f64, a 3x4 projection; margin >= 0.  In this order, without contraction:
+ *      d    = X - t
+ *      xc_k = R[0][k] d0 + R[1][k] d1 + R[2][k] d2          (R^T d, left to right)
+ *      h_i  = P[i][0] xc0 + P[i][1] xc1 + P[i][2] xc2 + P[i][3]
+ *      u = h0 / h2, v = h1 / h2
+ *    valid iff xc2 > min_depth, h2 > 0, margin <= u < W - margin and
+ *    margin <= v < H - margin.  d_uv [batch][x_cap][2] f32 = (float)u, (float)v,
+ *    both NaN when invalid; d_z [batch][x_cap] f64 = xc2 (may be NULL).  Rows
+ *    >= nx are not written.  batch <= 65535 (here and in step 3). */
+int slam_project_landmarks(const double* d_X, int x_shared, const int32_t* d_nx, int x_cap,
+                           int batch, const double* d_poses, const double* d_P, int W, int H,
+                           double margin, double min_depth, float* d_uv, double* d_z,
+                           void* stream);
+
+/* 2. Cell index of a batch of keypoint sets.  d_kp [batch][kp_cap][5] f32 (the
+ *    layout slam_orb_tiles writes: x, y first), d_nkp [batch] i32 (negative --
+ *    ORB's overflow code -- counts as 0, otherwise clamped to kp_cap);
+ *    cell in {16, 32, 64}; gw = ceil(W / cell), gh = ceil(H / cell), gw gh <=
+ *    16384; kp_cap <= 65535.  A keypoint with 0 <= x < W and 0 <= y < H goes to
+ *    cell (int)(y / cell) gw + (int)(x / cell); any other (NaN included) is left
+ *    out.  d_cell_ptr [batch][gw gh + 1] i32: CSR offsets in row-major cell
+ *    order; d_cell_kp [batch][kp_cap] i32: keypoint indices grouped by cell (the
+ *    order inside a cell is unspecified; entries past the total are not
+ *    written). */
+int slam_kp_grid(const float* d_kp, const int32_t* d_nkp, int kp_cap, int batch, int W, int H,
+                 int cell, int32_t* d_cell_ptr, int32_t* d_cell_kp, void* stream);
+
+/* 3. Windowed Hamming kNN-2.  Queries: d_q [q_items][q_cap][32] u8 (q_items =
+ *    batch, or 1 when q_shared != 0), d_quv [batch][q_cap][2] f32 window centre,
+ *    d_qr [batch][q_cap] f32 window half-size, d_nq [batch].  Targets: d_t
+ *    [batch][t_cap][32] u8, d_kp [batch][t_cap][5] f32, d_nt [batch] and the
+ *    index of step 2 built from the same d_kp with the same W, H, cell.
+ *    The result does not depend on the cell size.  For query i with finite u,
+ *    v and r > 0, keypoint j < nt inside the image (0 <= kx < W, 0 <= ky < H:
+ *    the keypoints step 2 indexes) is a candidate iff
+ *      fabsf(kx_j - u) <= r && fabsf(ky_j - v) <= r        (f32, edge included)
+ *    and the two smallest keys dist << 16 | j over the candidates are reported
+ *    (ties to the lower index, as slam_hamming_knn2):
+ *      d_idx2, d_dist2 [batch][q_cap][2] i32 (-1 = none)
+ *      d_good [batch][q_cap] u8 = 1 iff d1 exists, d1 <= max_dist and either
+ *             no second candidate exists or ratio_den d1 < ratio_num d2.
+ *    Unlike slam_hamming_knn2, ONE candidate is enough for a good match: a
+ *    single keypoint in a small window is the normal case, not a truncated
+ *    search.  A query with non-finite uv or r <= 0 gets -1 / -1 / 0; rows >= nq
+ *    are not written.  max_dist in 0..256, 0 < ratio_num <= ratio_den,
+ *    t_cap <= 65535, q_cap <= 1 << 20; descriptors 16-byte aligned. */
+int slam_hamming_window_knn2(const uint8_t* d_q, int q_shared, const float* d_quv,
+                             const float* d_qr, const int32_t* d_nq, int q_cap,
+                             const uint8_t* d_t, const float* d_kp, const int32_t* d_nt,
+                             int t_cap, const int32_t* d_cell_ptr, const int32_t* d_cell_kp,
+                             int W, int H, int cell, int batch, int max_dist, int ratio_num,
+                             int ratio_den, int32_t* d_idx2, int32_t* d_dist2, uint8_t* d_good,
+                             void* stream);
+
+/* 4. One landmark per keypoint.  A keypoint that is the best match (d_idx2[.][0])
+ *    of several good queries goes to the one with the smallest (d1, query
+ *    index): an integer atomicMin of d1 << 22 | query, so the result does not
+ *    depend on the order of arrival.  d_owner [batch][t_cap] i32 = the winning
+ *    query or -1; d_good_out [batch][q_cap] u8 = d_good with the losers cleared
+ *    (rows >= nq are not written; it may not alias d_good). */
+int slam_match_unique(const int32_t* d_idx2, const int32_t* d_dist2, const uint8_t* d_good,
+                      const int32_t* d_nq, int q_cap, int t_cap, int batch, int32_t* d_owner,
+                      uint8_t* d_good_out, void* stream);
+
+/* 5. Track rows.  d_rows [batch][rows_cap][4] f64 = [frame0 + b, landmark
+ *    index, (double)kx, (double)ky] for the good queries of step 4 in ascending
+ *    landmark order -- the row format of slam_map_associate -- and d_count
+ *    [batch] i32.  rows_cap >= min(q_cap, kp_cap) (after step 4 every keypoint
+ *    appears at most once); a smaller cap is an argument error. */
+int slam_track_rows(const int32_t* d_idx2, const uint8_t* d_good, const int32_t* d_nq, int q_cap,
+                    const float* d_kp, int kp_cap, int batch, int frame0, int rows_cap,
+                    double* d_rows, int32_t* d_count, void* stream);
+
+/* ------------------------------------------------------------------------
  * Tiled ORB detector + rBRIEF descriptor.
  *
  * Replaces orb_detector_using_tiles (/root/reference/orb.py:4-25), i.e. the

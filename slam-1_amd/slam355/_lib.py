@@ -109,6 +109,14 @@ SIGNATURES = {
                          c_p, c_size_t, c_p],
     "slam_map_associate": [c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_int, c_double, c_int,
                            c_p, c_p, c_size_t, c_p],
+    "slam_project_landmarks": [c_p, c_int, c_p, c_int, c_int, c_p, c_p, c_int, c_int, c_double,
+                               c_double, c_p, c_p, c_p],
+    "slam_kp_grid": [c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p],
+    "slam_hamming_window_knn2": [c_p, c_int, c_p, c_p, c_p, c_int, c_p, c_p, c_p, c_int, c_p, c_p,
+                                 c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_p, c_p, c_p,
+                                 c_p],
+    "slam_match_unique": [c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_p, c_p, c_p],
+    "slam_track_rows": [c_p, c_p, c_p, c_int, c_p, c_int, c_int, c_int, c_int, c_p, c_p, c_p],
     "slam_fundamental_lmeds": [c_p, c_p, c_p, c_int, c_int, c_uint64, c_int, c_int, c_p, c_p, c_p,
                                c_p],
     "slam_fundamental_lmeds_ws": [c_p, c_p, c_p, c_int, c_int, c_uint64, c_int, c_int, c_p, c_p,

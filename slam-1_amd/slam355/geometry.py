@@ -88,6 +88,29 @@ def filter_pairs(pairs, count, mask, out=None, stream=None):
     return o, oc
 
 
+def project_landmarks(X, nx, poses, P, W, H, margin=0.0, min_depth=0.1, out=None, stream=None):
+    """World points into `B` frames (slam_project_landmarks, step 1 of guided matching).
+
+    X [cap,3] f64 (one map shared by every frame) or [B,cap,3], nx [B] i32,
+    poses [B,4,4] f64 camera-to-world, P 3x4 (device tensor [3,4] f64, or an
+    array uploaded here) -> (uv [B,cap,2] f32, NaN where the point is not
+    visible; z [B,cap] f64 camera depth).  Rows >= nx[b] are left untouched
+    (NaN / 0 when allocated here)."""
+    B = int(poses.shape[0])
+    shared = X.dim() == 2
+    cap = int(X.shape[-2])
+    Pd = P if isinstance(P, torch.Tensor) else torch.as_tensor(np.asarray(P, np.float64),
+                                                               device=X.device)
+    if out is None:
+        uv = torch.full((B, cap, 2), float("nan"), dtype=torch.float32, device=X.device)
+        z = torch.zeros((B, cap), dtype=torch.float64, device=X.device)
+    else:
+        uv, z = out
+    _lib.call("slam_project_landmarks", ptr(X), int(shared), ptr(nx), cap, B, ptr(poses), ptr(Pd),
+              int(W), int(H), float(margin), float(min_depth), ptr(uv), ptr(z), stream_ptr(stream))
+    return uv, z
+
+
 def triangulate(ptl, ptr_, count, P_l, P_r, out=None, stream=None):
     """ptl/ptr [B,cap,2] f64, P 3x4 (shared) or [B,3,4] -> X [B,cap,3] f64."""
     B, cap, _ = ptl.shape

@@ -6,6 +6,11 @@ associates one frame's new absolute points with the map (exact nearest
 neighbour + the reference's |rel|-scaled gate) and appends the unmatched ones,
 all on the stream, so a sequence of frames runs without host synchronisation;
 the host only tracks an upper bound of M to size grids and grow the buffer.
+
+`LandmarkMap` keeps a descriptor per landmark as well and re-observes landmarks
+by projection: project the map with the predicted pose, search each landmark's
+descriptor among the keypoints in a window round its predicted pixel
+(slam_project_landmarks ... slam_track_rows; no counterpart in the reference).
 """
 from __future__ import annotations
 
@@ -14,7 +19,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, geometry, matcher
 from .device import ptr, require_gpu, stream_ptr, to_dev
 
 
@@ -77,6 +82,118 @@ class MapStore:
 
     def points(self) -> torch.Tensor:
         return self.map[: self.size()]
+
+
+class LandmarkMap:
+    """Landmarks with descriptors, matched to new frames by projection.
+
+    X [capacity,3] f64 world points and desc [capacity,32] u8 live on the
+    device; `add` appends (sizes known on the host).  `observe` projects the
+    map into a batch of frames with their predicted poses, searches every
+    landmark's descriptor among the keypoints within `radius` pixels of its
+    predicted position, gives each keypoint to at most one landmark and returns
+    the matches as [frame, landmark, x, y] rows -- the rows MapStore.append
+    writes, so `tracks()` feeds XXXport_files.problem_from_map directly.  All
+    of it runs on the stream without a host synchronisation."""
+
+    def __init__(self, capacity, kp_cap, W, H, P, cell=32):
+        self.dev = require_gpu()
+        self.cap, self.kp_cap = int(capacity), int(kp_cap)
+        self.W, self.H, self.cell = int(W), int(H), int(cell)
+        self.P = to_dev(np.ascontiguousarray(P, np.float64).reshape(3, 4))
+        self.X = torch.zeros((self.cap, 3), dtype=torch.float64, device=self.dev)
+        self.desc = torch.zeros((self.cap, 32), dtype=torch.uint8, device=self.dev)
+        self.n = 0
+        self._bufs = {}      # batch size -> the device buffers of observe
+        self._tracks = []    # (rows, count) of every observe call
+        self.uv = self.z = self.idx2 = self.dist2 = self.good = self.owner = None
+
+    def add(self, X, desc):
+        """Append landmarks: X [k,3] f64, desc [k,32] u8 (host arrays or tensors)."""
+        X = to_dev(X, torch.float64).reshape(-1, 3)
+        desc = to_dev(desc, torch.uint8).reshape(-1, 32)
+        k = int(X.shape[0])
+        if int(desc.shape[0]) != k:
+            raise ValueError("LandmarkMap.add: X and desc differ in length")
+        if self.n + k > self.cap:
+            raise ValueError(f"LandmarkMap.add: capacity {self.cap} < {self.n} + {k}")
+        self.X[self.n:self.n + k] = X
+        self.desc[self.n:self.n + k] = desc
+        self.n += k
+        return self
+
+    def _buffers(self, B):
+        b = self._bufs.get(B)
+        if b is None:
+            i32 = dict(dtype=torch.int32, device=self.dev)
+            kp0 = torch.zeros((B, self.kp_cap, 5), dtype=torch.float32, device=self.dev)
+            b = dict(
+                nq=torch.zeros((B,), **i32),
+                uv=torch.full((B, self.cap, 2), float("nan"), dtype=torch.float32, device=self.dev),
+                z=torch.zeros((B, self.cap), dtype=torch.float64, device=self.dev),
+                qr=torch.zeros((B, self.cap), dtype=torch.float32, device=self.dev),
+                grid=matcher.KeypointGrid(kp0, torch.zeros((B,), **i32), self.W, self.H, self.cell),
+                idx2=torch.full((B, self.cap, 2), -1, **i32),
+                dist2=torch.full((B, self.cap, 2), -1, **i32),
+                good0=torch.zeros((B, self.cap), dtype=torch.uint8, device=self.dev),
+                good=torch.zeros((B, self.cap), dtype=torch.uint8, device=self.dev),
+                owner=torch.full((B, max(self.kp_cap, 1)), -1, **i32),
+            )
+            self._bufs[B] = b
+        return b
+
+    def observe(self, frame0, poses, kp, desc, n_kp, radius=15.0, max_dist=64, ratio=(7, 10),
+                margin=0.0, min_depth=0.1, stream=None):
+        """poses [B,4,4] f64 camera-to-world (predicted), kp [B,kp_cap,5] f32,
+        desc [B,kp_cap,32] u8, n_kp [B] i32 -> (rows [B,min(capacity,kp_cap),4]
+        f64, count [B] i32) on the device.  `uv`, `z`, `idx2`, `dist2`, `good`
+        (after the uniqueness pass) and `owner` stay as attributes; they are
+        overwritten by the next call of the same batch size."""
+        B = int(poses.shape[0])
+        if tuple(kp.shape) != (B, self.kp_cap, 5) or tuple(desc.shape) != (B, self.kp_cap, 32):
+            raise ValueError("LandmarkMap.observe: kp / desc do not match (B, kp_cap)")
+        b = self._buffers(B)
+        with torch.cuda.stream(stream):  # the fills below follow the current stream
+            b["nq"].fill_(self.n)
+            b["qr"].fill_(float(radius))
+            uv, z = geometry.project_landmarks(self.X, b["nq"], poses, self.P, self.W, self.H,
+                                               margin=margin, min_depth=min_depth,
+                                               out=(b["uv"], b["z"]))
+            grid = b["grid"].build(kp, n_kp)
+            idx2, dist2, good0 = matcher.window_knn2_batch(
+                self.desc, uv, b["qr"], b["nq"], desc, kp, n_kp, grid, max_dist=max_dist,
+                ratio=ratio, out=(b["idx2"], b["dist2"], b["good0"]))
+            owner, good = matcher.unique_matches(idx2, dist2, good0, b["nq"], self.kp_cap,
+                                                 out=(b["owner"], b["good"]))
+            # fresh outputs per call: the caller keeps them while later frames run
+            rows = torch.zeros((B, max(min(self.cap, self.kp_cap), 1), 4), dtype=torch.float64,
+                               device=self.dev)
+            count = torch.zeros((B,), dtype=torch.int32, device=self.dev)
+            matcher.track_rows(idx2, good, b["nq"], kp, frame0, out=(rows, count))
+        self.uv, self.z, self.idx2, self.dist2, self.good, self.owner = uv, z, idx2, dist2, good, owner
+        self._tracks.append((rows, count))
+        return rows, count
+
+    def reset_tracks(self):
+        """Forget the rows kept for `tracks()` (the landmarks stay)."""
+        self._tracks = []
+
+    def tracks(self, compact=False):
+        """Synchronises: the rows of every observe call so far, concatenated
+        ([n,4] f64: frame, landmark, x, y) -- problem_from_map's optimization
+        matrix.  With compact=True the landmarks that were never observed are
+        left out: returns (rows with the landmark column renumbered, ids) where
+        ids [k] are the map indices, so X[ids] are the problem's points."""
+        out = [np.zeros((0, 4))]
+        for rows, count in self._tracks:
+            r, c = rows.cpu().numpy(), count.cpu().numpy()
+            out += [r[i, :c[i]] for i in range(len(c))]
+        om = np.concatenate(out, 0)
+        if not compact:
+            return om
+        ids, inv = np.unique(om[:, 1].astype(np.int64), return_inverse=True)
+        om[:, 1] = inv.reshape(-1)
+        return om, ids
 
 
 def appendKeyPoints(Qs, absPoint, threshold, points_2d, frame_index, rel_point):
