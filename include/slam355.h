@@ -426,7 +426,7 @@ int slam_ba_jacobian(const double* d_cams, const double* d_pts, const int32_t* d
 #define SLAM_BA_ST_SLOTS 20
 
 /* Everything the LM iteration touches; all pointers are device pointers.
- * Built by the host planner (slam355/ba.py): observations sorted by
+ * Built by the host planner (slam355/ba_plan.py): observations sorted by
  * (point, camera); index tables are fixed for the life of a problem. */
 typedef struct slam_ba_problem {
   int32_t n_cams, n_pts, n_obs;
@@ -490,7 +490,7 @@ typedef struct slam_ba_problem {
   const int32_t* chk_cptr;      /* [n_grps][8] start of each camera's run in chk_cobs */
   const int32_t* bslot_ab;      /* [n_bslots] camera pair a | b << 8 (a < b) of a block slot */
   /* Level schedule of the tiled solve (required when 9C > 120), built by
-   * slam355/ba.py tl_schedule: tiles of whole cameras (64-row tiles, the rows
+   * slam355/ba_plan.py tl_schedule: tiles of whole cameras (64-row tiles, the rows
    * past a tile's cameras padding) in nested-dissection order, with the row
    * maps between S and the tiled system, columns grouped by elimination-tree
    * level, the dataflow solve's column table, epilogue and gather tables and
@@ -562,7 +562,7 @@ int slam_ba_problem_size(void);
 #endif
 
 /* ---- host planner of the camera-union linearisation (lin_mode 1) ----------
- * slam355/ba.py plan_mfma in native code (the same tables, element for
+ * slam355/ba_plan.py plan_mfma in native code (the same tables, element for
  * element; no HIP call, callable without a GPU): observations sorted by
  * (point, camera), points renumbered by camera span, chunks of <= 120
  * observations / 16 points, supergroups of <= chunks_per_wg chunks seeing
@@ -624,11 +624,30 @@ int slam_ba_stage_windows(int n_win, int n, int cap, const double* rows, const i
                           double u_off, double v_off, double* h64, long long cap64, int32_t* h32,
                           long long cap32, const void* d64, const void* d32,
                           slam_ba_problem* probs, long long* meta, long long* need);
+/* The float64 layout of one BA problem (host only, no GPU call): the
+ * SLAM_STAGE_NF64 segments in the order listed above, len[k] doubles each
+ * (cams 9C, pts 3P, obs_q 2 max(O, 1), camrec 32C, cpart 112 n_cslots, bpart
+ * 81 n_bslots, sys slam_ba_sys_len(n_cams, n_blocks), chol chol_len, delta_c
+ * 9C, red_part slam_ba_red_slots(n_grps), small 4, state SLAM_BA_ST_SLOTS; a
+ * workspace keeps at least one element), off[k] the segment's start relative
+ * to the problem's first double (every start a multiple of 32 doubles), *total
+ * the aligned length of the whole.  chol_len: slam_ba_chol_len for a tiled
+ * solve (9C > 120), 0 otherwise.  slam_ba_stage_windows lays every window out
+ * with it; slam355/ba.py allocates BAProblem and BAWindowSet.build from it. */
+int slam_ba_f64_layout(int n_cams, int n_pts, int n_obs, int n_grps, int n_cslots, int n_bslots,
+                       int n_blocks, long long chol_len, long long len[SLAM_STAGE_NF64],
+                       long long off[SLAM_STAGE_NF64], long long* total);
+/* The int32 words of one staged problem whose plan has plan_len words: the
+ * plan tables, then 8 zero words (from plan_len: the one-element stand-ins of
+ * the lin_mode-0 tables; at *ticket = plan_len + 4: the completion ticket;
+ * *end = plan_len + 8), rounded up to a multiple of 32.  Returns that length
+ * (0 on plan_len < 0); ticket and end may be null. */
+long long slam_ba_i32_layout(long long plan_len, long long* ticket, long long* end);
 
 /* Number of doubles red_part needs for a problem with n_grps point groups. */
 int slam_ba_red_slots(int n_grps);
 /* Doubles of the tiled-Cholesky workspace `chol` (needed only when 9C > 120)
- * for a tile schedule (the host copy tl_sched_host, slam355/ba.py
+ * for a tile schedule (the host copy tl_sched_host, slam355/ba_plan.py
  * tl_schedule): its tile count tl_sched_host[1] (a schedule of whole-camera
  * tiles may have more tiles than 9C / 64) and its product slots
  * tl_sched_host[11] (the 64x64 terms L_Ik L_Jk^T that column k forms for

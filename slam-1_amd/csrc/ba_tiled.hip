@@ -91,7 +91,7 @@ constexpr int kVR = 65;   // row stride of k_tl3_flow's row-major L_JJ^-1
 
 // ---------------------------------------------------------------- level-scheduled tiled solve
 // The same tile factor with the columns grouped by elimination-tree level
-// (slam355/ba.py tl_schedule: tiles renumbered by nested dissection of the
+// (slam355/ba_plan.py tl_schedule: tiles renumbered by nested dissection of the
 // tile graph, symbolic structure on the host).  Per level: k_tl2_panel (WG per
 // (k, I) of every column k of the level: the diagonal WG stores L_kk^-1 and
 // y_k = L_kk^-1 b_k, the others L_Ik = A_Ik L_kk^-T), then k_tl2_update (WG
@@ -240,7 +240,7 @@ __global__ __launch_bounds__(1024) void k_tl2_epilogue(slam_ba_problem p, int T_
 // ---------------------------------------------------------------- dataflow tiled solve
 // The same factor as a dataflow graph in ONE launch: workgroup J owns tile
 // column J (new numbering) for the whole solve and, from the schedule's column
-// table (slam355/ba.py tl_schedule),
+// table (slam355/ba_plan.py tl_schedule),
 //   (1) A_JJ -= sum_{k in rs(J)} L_Jk L_Jk^T  (waits for each L_Jk's flag),
 //       factor + inverse of the diagonal tile (tile_chol_inv_blk, from LDS);
 //   (2) per row tile I in rows(J), parent first: A_IJ -= sum_k L_Ik L_Jk^T,

@@ -23,12 +23,34 @@
 
 namespace {
 using i64 = long long;
-constexpr int kNState = SLAM_BA_ST_SLOTS;
-i64 al32(i64 n) { return (std::max<i64>(n, 1) + 31) / 32 * 32; }  // BAWindowSet._al
+static_assert(SLAM_BA_F64_COUNT == SLAM_STAGE_NF64, "ba_layout.hpp lists every float64 segment");
 }  // namespace
 
-extern "C" int slam_ba_red_slots(int n_grps);
-extern "C" long long slam_ba_sys_len(int n_cams, int n_blocks);
+extern "C" int slam_ba_f64_layout(int n_cams, int n_pts, int n_obs, int n_grps, int n_cslots,
+                                  int n_bslots, int n_blocks, long long chol_len,
+                                  long long len[SLAM_STAGE_NF64], long long off[SLAM_STAGE_NF64],
+                                  long long* total) {
+  SLAM_REQUIRE(n_cams >= 0 && n_pts >= 0 && n_obs >= 0 && n_grps >= 0 && n_cslots >= 0 &&
+                   n_bslots >= 0 && n_blocks >= 0 && chol_len >= 0,
+               "slam_ba_f64_layout: bad sizes");
+  SLAM_REQUIRE(len && off && total, "slam_ba_f64_layout: null output");
+  ba_f64_lengths(n_cams, n_pts, n_obs, n_cslots, n_bslots, slam_ba_sys_len(n_cams, n_blocks), chol_len,
+                 slam_ba_red_slots(n_grps), SLAM_BA_ST_SLOTS, len);
+  i64 o = 0;
+  for (int k = 0; k < SLAM_BA_F64_COUNT; ++k) {
+    off[k] = o;
+    o += ba_aligned(len[k]);
+  }
+  *total = o;
+  return SLAM_OK;
+}
+
+extern "C" long long slam_ba_i32_layout(long long plan_len, long long* ticket, long long* end) {
+  if (plan_len < 0) return 0;
+  if (ticket) *ticket = plan_len + kI32Ticket;
+  if (end) *end = plan_len + kI32Tail;
+  return ba_aligned(plan_len + kI32Tail);
+}
 
 extern "C" int slam_ba_stage_windows(int n_win, int n, int cap, const double* rows,
                                      const int32_t* cnt, const double* maps, int map_cap,
@@ -78,23 +100,18 @@ extern "C" int slam_ba_stage_windows(int n_win, int n, int cap, const double* ro
     const int rc = slam_ba_plan_mfma(C, P, O, ci.data(), pi.data(), nullptr, 0, 0, plan.data(), bound,
                                      &info);
     if (rc != SLAM_OK) return rc;
-    // 9C <= 120: the one-workgroup solve (ba.py LDS_MAX_N)
+    // 9C <= 120: the one-workgroup solve (ba_plan.py LDS_MAX_N)
     if (!info.ok || 9 * C > 120) continue;  // mt[0] = 0: not staged
     const int G = info.n_grps, n_cs = info.n_cslots, n_bs = info.n_bslots, NB = info.n_blocks;
-    const i64 sys_len = slam_ba_sys_len(C, NB), red = slam_ba_red_slots(G);
-    // float64 layout (BAWindowSet.build): parameters twice, initial copy,
+    // float64 layout (ba_layout.hpp): parameters twice, initial copy,
     // observations in plan order, then the zeroed workspaces
-    const i64 len64[SLAM_STAGE_NF64] = {9ll * C, 3ll * P, 9ll * C, 3ll * P, 9ll * C, 3ll * P,
-                                        2ll * std::max(O, 1), (i64)kCamRec * C, (i64)kCamRec * C,
-                                        (i64)kCPart * n_cs, 81ll * n_bs, sys_len, 1, 9ll * C, red, 4,
-                                        kNState};
-    i64 off64[SLAM_STAGE_NF64];
-    for (int k = 0; k < SLAM_STAGE_NF64; ++k) {
-      off64[k] = o64;
-      o64 += al32(len64[k]);
-    }
+    i64 len64[SLAM_STAGE_NF64], off64[SLAM_STAGE_NF64], n64, tick;
+    if (const int lrc = slam_ba_f64_layout(C, P, O, G, n_cs, n_bs, NB, 0, len64, off64, &n64)) return lrc;
+    for (i64& o : off64) o += o64;
+    o64 += n64;
+    const i64 sys_len = len64[SLAM_BA_F64_SYS];
     const i64 nb = info.total, w32 = o32;
-    o32 += al32(nb + 8);  // plan tables, 4 one-element stand-ins, ticket
+    o32 += slam_ba_i32_layout(nb, &tick, nullptr);  // plan tables, stand-ins, ticket
     mt[0] = 1;
     mt[4] = G;
     mt[5] = info.n_sgrps;
@@ -113,12 +130,12 @@ extern "C" int slam_ba_stage_windows(int n_win, int n, int cap, const double* ro
     const double* cw = cams + (size_t)w * n * 9;
     const double* mp = maps + (size_t)w * map_cap * 3;
     for (int rep = 0; rep < 3; ++rep) {  // cams0 / pts0, cams1 / pts1, init_c / init_p
-      std::memcpy(h64 + off64[2 * rep], cw, sizeof(double) * 9 * C);
-      double* pd = h64 + off64[2 * rep + 1];
+      std::memcpy(h64 + off64[SLAM_BA_F64_CAMS0 + 2 * rep], cw, sizeof(double) * 9 * C);
+      double* pd = h64 + off64[SLAM_BA_F64_PTS0 + 2 * rep];
       for (int k = 0; k < P; ++k)
         for (int c = 0; c < 3; ++c) pd[3 * k + c] = mp[3 * (size_t)perm[k] + c];
     }
-    double* oq = h64 + off64[6];
+    double* oq = h64 + off64[SLAM_BA_F64_OBS_Q];
     if (O == 0) {
       oq[0] = oq[1] = 0.0;
     } else {
@@ -127,10 +144,11 @@ extern "C" int slam_ba_stage_windows(int n_win, int n, int cap, const double* ro
         oq[2 * k + 1] = qs[2 * (size_t)order[k] + 1];
       }
     }
-    for (int k = 7; k < SLAM_STAGE_NF64; ++k) std::memset(h64 + off64[k], 0, sizeof(double) * len64[k]);
+    for (int k = kF64Zeroed; k < SLAM_STAGE_NF64; ++k)
+      std::memset(h64 + off64[k], 0, sizeof(double) * len64[k]);
     // ---- int32: the plan tables, then zeros (stand-ins of the lin_mode-0 tables, ticket)
     std::memcpy(h32 + w32, plan.data(), sizeof(int32_t) * nb);
-    std::memset(h32 + w32 + nb, 0, sizeof(int32_t) * 8);
+    std::memset(h32 + w32 + nb, 0, sizeof(int32_t) * kI32Tail);
     // ---- the descriptor, with device addresses
     double* D = reinterpret_cast<double*>(const_cast<void*>(d64));
     int32_t* I = reinterpret_cast<int32_t*>(const_cast<void*>(d32));
@@ -149,22 +167,22 @@ extern "C" int slam_ba_stage_windows(int n_win, int n, int cap, const double* ro
     s.lin_mode = 1;
     s.n_sgrps = info.n_sgrps;
     s.tl_mode = 0;
-    s.cams[0] = D + off64[0];
-    s.pts[0] = D + off64[1];
-    s.cams[1] = D + off64[2];
-    s.pts[1] = D + off64[3];
-    s.camrec[0] = D + off64[7];
-    s.camrec[1] = D + off64[8];
-    s.obs_q = D + off64[6];
-    s.cpart = D + off64[9];
-    s.bpart = D + off64[10];
-    s.sys = D + off64[11];
-    s.chol = D + off64[12];
-    s.delta_c = D + off64[13];
-    s.red_part = D + off64[14];
-    s.small = D + off64[15];
-    s.state = D + off64[16];
-    s.ticket = reinterpret_cast<uint32_t*>(I + w32 + nb + 4);
+    s.cams[0] = D + off64[SLAM_BA_F64_CAMS0];
+    s.pts[0] = D + off64[SLAM_BA_F64_PTS0];
+    s.cams[1] = D + off64[SLAM_BA_F64_CAMS1];
+    s.pts[1] = D + off64[SLAM_BA_F64_PTS1];
+    s.camrec[0] = D + off64[SLAM_BA_F64_CAMREC0];
+    s.camrec[1] = D + off64[SLAM_BA_F64_CAMREC1];
+    s.obs_q = D + off64[SLAM_BA_F64_OBS_Q];
+    s.cpart = D + off64[SLAM_BA_F64_CPART];
+    s.bpart = D + off64[SLAM_BA_F64_BPART];
+    s.sys = D + off64[SLAM_BA_F64_SYS];
+    s.chol = D + off64[SLAM_BA_F64_CHOL];
+    s.delta_c = D + off64[SLAM_BA_F64_DELTA_C];
+    s.red_part = D + off64[SLAM_BA_F64_RED_PART];
+    s.small = D + off64[SLAM_BA_F64_SMALL];
+    s.state = D + off64[SLAM_BA_F64_STATE];
+    s.ticket = reinterpret_cast<uint32_t*>(I + w32 + tick);
     s.obs_cam = tab + info.off[SLAM_PLAN_OBS_CAM];
     s.obs_pt = tab + info.off[SLAM_PLAN_OBS_PT];
     s.pt_ptr = tab + info.off[SLAM_PLAN_PT_PTR];

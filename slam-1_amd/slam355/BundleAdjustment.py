@@ -163,7 +163,7 @@ def _bal_sparsity(n_cams, n_Qs, cam_idxs, Q_idxs):
     """The 2x12-per-observation Jacobian pattern as a scipy lil_matrix of ints.
 
     Host-side index bookkeeping (the GPU solver derives the same structure
-    itself, slam355/ba.py:plan)."""
+    itself, slam355/ba_plan.py:plan)."""
     from scipy.sparse import coo_matrix
 
     cam_idxs = np.asarray(cam_idxs, np.int64)

@@ -191,9 +191,12 @@ SIGNATURES = {
                           ctypes.POINTER(PlanInfo)],
     "slam_ba_stage_windows": [c_int, c_int, c_int, c_p, c_p, c_p, c_int, c_p, c_p, c_double,
                               c_double, c_p, c_longlong, c_p, c_longlong, c_p, c_p, c_p, c_p, c_p],
+    "slam_ba_f64_layout": [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_longlong, c_p, c_p,
+                           c_p],
+    "slam_ba_i32_layout": [c_longlong, c_p, c_p],
 }
 _RESTYPE = {"slam_last_error": ctypes.c_char_p, "slam_ba_sys_len": ctypes.c_longlong,
-            "slam_ba_plan_bound": ctypes.c_longlong,
+            "slam_ba_plan_bound": ctypes.c_longlong, "slam_ba_i32_layout": ctypes.c_longlong,
             "slam_ba_chol_len": ctypes.c_longlong, "slam_ba_cov_workspace_len": ctypes.c_longlong,
             "slam_pnp_workspace_len": ctypes.c_longlong,
             "slam_pnp_scratch_len": ctypes.c_longlong,

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from oracle import ba as oba
+from stage_ref import stage_inputs, synthetic_windows
 
 
 @pytest.fixture(scope="module")
@@ -1115,43 +1116,6 @@ def test_gpu_window_set_equals_separate_problems():
             assert np.array_equal(r[w][0], rc) and np.array_equal(r[w][1], rp), w
 
 
-def _stage_inputs(specs, n, seed, u_off=0.5, v_off=0.25):
-    """Mapper-shaped host arrays (rows [W n, cap, 4] = (frame, point, u, v),
-    counts, maps, M, cams) for synthetic windows of n cameras, each window's
-    observations dealt over its n pairs in order, and the problems they stand
-    for (q = u - u_off: the stager's arithmetic)."""
-    from slam355.synthetic import ba_problem, perturb
-
-    wins = []
-    for w, (P, k) in enumerate(specs):
-        rng = np.random.default_rng(seed + w)
-        cams, pts, ci, pi, qs = ba_problem(rng, n, P, k)
-        c0, p0 = perturb(rng, cams, pts)
-        wins.append((c0, p0, ci, pi, qs))
-    W = len(wins)
-    cap = max(-(-len(w[2]) // n) for w in wins)
-    map_cap = max(len(w[1]) for w in wins)
-    rows = np.zeros((W * n, cap, 4))
-    cnt = np.zeros(W * n, np.int32)
-    maps = np.zeros((W, map_cap, 3))
-    M = np.zeros(W, np.int32)
-    cams = np.zeros((W * n, 9))
-    probs = []
-    for w, (c0, p0, ci, pi, qs) in enumerate(wins):
-        maps[w, :len(p0)] = p0
-        M[w] = len(p0)
-        cams[w * n:(w + 1) * n] = c0
-        parts = np.array_split(np.arange(len(ci)), n)
-        qq = []
-        for j, idx in enumerate(parts):
-            b = w * n + j
-            cnt[b] = len(idx)
-            rows[b, :len(idx)] = np.stack([ci[idx], pi[idx], qs[idx, 0] + u_off, qs[idx, 1] + v_off], 1)
-            qq.append(np.stack([rows[b, :len(idx), 2] - u_off, rows[b, :len(idx), 3] - v_off], 1))
-        probs.append((c0, p0, ci, pi, np.concatenate(qq)))
-    return (rows, cnt, maps, M, cams, u_off, v_off), probs
-
-
 def test_stage_windows_layout_matches_planner():
     """slam_ba_stage_windows (host only, fake device addresses): per window the
     native planner's tables, the float64 data in BAProblem's layout (points
@@ -1162,7 +1126,8 @@ def test_stage_windows_layout_matches_planner():
 
     from slam355 import _lib, ba
 
-    (rows, cnt, maps, M, cams, uo, vo), probs = _stage_inputs([(800, 3), (300, 8), (1000, 2)], 8, 70)
+    wins = synthetic_windows([(800, 3), (300, 8), (1000, 2)], 8, 70)
+    (rows, cnt, maps, M, cams, uo, vo), probs = stage_inputs(wins, 8)
     W = len(probs)
     meta = np.zeros((W, ba.BAWindowSet.META), np.int64)
     need = np.zeros(2, np.int64)
@@ -1181,7 +1146,13 @@ def test_stage_windows_layout_matches_planner():
         c0, p0, ci, pi, qs = probs[w]
         pl = ba.plan_mfma_native(8, len(p0), ci, pi)
         m = meta[w]
-        _, _, o64, o32, nb, offs = ba.BAWindowSet._views_of(h64, h32, m)
+        pc = ba.BAWindowSet._placed(m)
+        lay = ba._Layout(pc.sizes)
+        # the layout rebuilt from the meta row's sizes is the staged one
+        assert [pc.o64 + lay.off[k] for k in lay.names] == [int(v) for v in m[12:12 + len(lay.names)]]
+        assert lay.shape["sys"] == (int(m[11]),)
+        o64 = {k: (pc.o64 + lay.off[k], lay.shape[k]) for k in lay.names}
+        o32, nb, offs = pc.o32, pc.nb, pc.offs
         assert nb == len(pl["buf"]) and np.array_equal(h32[o32:o32 + nb], pl["buf"])
         assert np.all(h32[o32 + nb:o32 + nb + 8] == 0)
         get = lambda k: h64[o64[k][0]:o64[k][0] + int(np.prod(o64[k][1]))].reshape(o64[k][1])  # noqa: E731
@@ -1190,13 +1161,81 @@ def test_stage_windows_layout_matches_planner():
         for k in ("pts0", "pts1", "init_p"):
             assert np.array_equal(get(k), p0[pl["perm"]])
         assert np.array_equal(get("obs_q"), qs[pl["order"]])
-        for k in ba.BAWindowSet._F64[7:]:
+        for k in lay.names[len(lay.uploaded):]:
             assert np.all(get(k) == 0.0), k
         s = structs[w]
         assert (s.n_cams, s.n_pts, s.n_obs, s.n_sgrps) == (8, len(p0), len(ci), pl["n_sgrps"])
         assert s.cams[1] == d64 + 8 * o64["cams1"][0] and s.state == d64 + 8 * o64["state"][0]
         assert s.obs_meta == d32 + 4 * (o32 + offs["obs_meta"])
         assert s.ticket == d32 + 4 * (o32 + nb + 4)
+
+
+def test_f64_layout_table():
+    """slam_ba_f64_layout against the layout restated here once, as (name,
+    length) in memory order, every segment rounded up to 32 doubles: a shape
+    where obs_q, cpart and bpart clamp to their minimum, a tiny and a tracked
+    window (whose slam_ba_stage_windows meta offsets are the same table) and a
+    tiled problem (9C > 120) with its real slam_ba_chol_len."""
+    from slam355 import _lib, ba
+    from slam355.synthetic import ba_problem
+
+    def table(C, P, O, G, n_cs, n_bs, NB, chol_len):
+        sys_len = (81 * NB if 9 * C > 120 else (9 * C) ** 2) + 3 * 9 * C + C
+        assert sys_len == _lib.lib.slam_ba_sys_len(C, NB)
+        return [("cams0", 9 * C), ("pts0", 3 * P), ("cams1", 9 * C), ("pts1", 3 * P), ("init_c", 9 * C),
+                ("init_p", 3 * P), ("obs_q", 2 * max(O, 1)), ("camrec0", 32 * C), ("camrec1", 32 * C),
+                ("cpart", max(112 * n_cs, 1)), ("bpart", max(81 * n_bs, 1)), ("sys", sys_len),
+                ("chol", max(chol_len, 1)), ("delta_c", 9 * C), ("red_part", _lib.lib.slam_ba_red_slots(G)),
+                ("small", 4), ("state", 20)]
+
+    def check(sizes, chol_len=0):
+        want = table(*sizes, chol_len)
+        n = len(want)
+        ln, off = np.full(n, -1, np.int64), np.full(n, -1, np.int64)
+        total = np.full(1, -1, np.int64)
+        _lib.call("slam_ba_f64_layout", *sizes, chol_len, ln.ctypes.data, off.ctypes.data, total.ctypes.data)
+        assert list(ln) == [v for _, v in want]
+        pad = [(max(v, 1) + 31) // 32 * 32 for _, v in want]  # (an empty segment takes one unit)
+        assert list(off) == [sum(pad[:i]) for i in range(n)] and int(total[0]) == sum(pad)
+        lay = ba._Layout(sizes, chol_len)
+        assert lay.names == tuple(k for k, _ in want) and lay.total == sum(pad)
+        assert [lay.off[k] for k in lay.names] == list(off)
+        assert [int(np.prod(lay.shape[k])) for k in lay.names] == list(ln)
+        return list(off), sum(pad)
+
+    def planned(C, pts, ci, pi, **kw):
+        pl = ba.plan_mfma_native(C, len(pts), ci, pi, **kw)
+        return (C, len(pts), pl["n_obs"], pl["n_grps"], len(pl["cslot_cam"]), len(pl["bslot_blk"]),
+                len(pl["blocks"]))
+
+    check((2, 3, 0, 1, 0, 0, 3))  # no observation, no slot: obs_q, cpart, bpart at their minimum
+    rng = np.random.default_rng(3)
+    tiny = (rng.normal(size=(2, 9)), rng.normal(size=(4, 3)), np.tile([0, 1], 4), np.repeat(np.arange(4), 2),
+            rng.normal(size=(8, 2)))
+    cams, pts, ci, pi, qs = ba_problem(np.random.default_rng(4), 8, 300, 3)
+    for win in (tiny, (cams, pts, ci, pi, qs)):
+        C = len(win[0])
+        sizes = planned(C, win[1], win[2], win[3])
+        assert sizes[2] == len(win[2]) > 0
+        off, total = check(sizes)
+        # the same window staged twice: the second one's offsets start at the first one's total
+        (rows, cnt, maps, M, cc, uo, vo), _ = stage_inputs([win, win], C)
+        meta = np.zeros((2, ba.BAWindowSet.META), np.int64)
+        need = np.zeros(2, np.int64)
+        _lib.call("slam_ba_stage_windows", 2, C, rows.shape[1], rows.ctypes.data, cnt.ctypes.data,
+                  maps.ctypes.data, maps.shape[1], M.ctypes.data, cc.ctypes.data, uo, vo, None, 0, None, 0,
+                  None, None, None, meta.ctypes.data, need.ctypes.data)
+        assert list(meta[:, 0]) == [1, 1] and int(need[0]) == 2 * total
+        for w in (0, 1):
+            assert list(meta[w, 12:12 + len(off)]) == [w * total + o for o in off]
+    # tiled: 14 cameras (9C = 126 > 120), packed blocks, the schedule's workspace
+    cams, pts, ci, pi, qs = ba_problem(np.random.default_rng(5), 14, 200, 3)
+    bl = ba.upper_blocks(14, ci, pi)
+    sizes = planned(14, pts, ci, pi, block_list=bl)
+    sched = ba.tl_schedule(14, ba.plan_mfma_native(14, len(pts), ci, pi, bl)["blocks"])
+    chol_len = int(_lib.lib.slam_ba_chol_len(14, sched.ctypes.data))
+    assert chol_len > 1 and sizes[6] == len(bl)
+    check(sizes, chol_len)
 
 
 @pytest.mark.gpu
@@ -1208,7 +1247,7 @@ def test_gpu_window_stage_equals_separate_problems():
     import torch
     from slam355 import ba
 
-    inp, probs = _stage_inputs([(800, 3), (300, 8), (1000, 2)], 8, 80)
+    inp, probs = stage_inputs(synthetic_windows([(800, 3), (300, 8), (1000, 2)], 8, 80), 8)
     s = torch.cuda.Stream()
     ws = ba.BAWindowSet()
     runs = []

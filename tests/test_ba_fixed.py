@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 from oracle import ba as oba
+from stage_ref import stage_inputs, synthetic_windows
 
 
 def make_problem(seed, C, P, obs_per_pt):
@@ -278,38 +279,6 @@ def test_gpu_fixed_in_batch_equals_solo():
     assert not np.array_equal(solo[1].params()[0][:, 6:], w1[0][:, 6:])  # the free intrinsics did
 
 
-def _stage_inputs(specs, n, seed, u_off=0.5, v_off=0.25):
-    """Mapper-shaped host arrays for windows of n cameras (rows [W n, cap, 4] =
-    (frame, point, u, v), counts, maps, M, cams) and the problems they stand for."""
-    from slam355.synthetic import ba_problem, perturb
-
-    wins = []
-    for w, (P, k) in enumerate(specs):
-        rng = np.random.default_rng(seed + w)
-        cams, pts, ci, pi, qs = ba_problem(rng, n, P, k)
-        wins.append((*perturb(rng, cams, pts), ci, pi, qs))
-    W = len(wins)
-    cap = max(-(-len(w[2]) // n) for w in wins)
-    rows = np.zeros((W * n, cap, 4))
-    cnt = np.zeros(W * n, np.int32)
-    maps = np.zeros((W, max(len(w[1]) for w in wins), 3))
-    M = np.zeros(W, np.int32)
-    cams = np.zeros((W * n, 9))
-    probs = []
-    for w, (c0, p0, ci, pi, qs) in enumerate(wins):
-        maps[w, :len(p0)] = p0
-        M[w] = len(p0)
-        cams[w * n:(w + 1) * n] = c0
-        qq = []
-        for j, idx in enumerate(np.array_split(np.arange(len(ci)), n)):
-            b = w * n + j
-            cnt[b] = len(idx)
-            rows[b, :len(idx)] = np.stack([ci[idx], pi[idx], qs[idx, 0] + u_off, qs[idx, 1] + v_off], 1)
-            qq.append(np.stack([rows[b, :len(idx), 2] - u_off, rows[b, :len(idx), 3] - v_off], 1))
-        probs.append((c0, p0, ci, pi, np.concatenate(qq)))
-    return (rows, cnt, maps, M, cams, u_off, v_off), probs
-
-
 @pytest.mark.gpu
 def test_gpu_window_set_fixed_equals_separate_problems():
     """BAWindowSet.build(fixed=) and .stage(fixed=) give every window the
@@ -320,7 +289,7 @@ def test_gpu_window_set_fixed_equals_separate_problems():
     import torch
     from slam355 import ba
 
-    inp, probs = _stage_inputs([(800, 3), (300, 8), (1000, 2)], 8, 80)
+    inp, probs = stage_inputs(synthetic_windows([(800, 3), (300, 8), (1000, 2)], 8, 80), 8)
     s = torch.cuda.Stream()
     ws = ba.BAWindowSet()
     fx = np.tile(ba.FIXED_INTRINSICS, (8, 1))

@@ -33,6 +33,7 @@ import numpy as np
 import pytest
 
 from oracle import ba as oba
+from stage_ref import stage_inputs
 
 DELTA = 1.5
 LAM0 = 1e-4
@@ -568,32 +569,6 @@ def test_gpu_window_set_loss_equals_separate_problems():
                 assert np.array_equal(x, y)
 
 
-def _stage_inputs(wins, n, u_off=0.5, v_off=0.25):
-    """Mapper-shaped host arrays (rows [W n, cap, 4] = (frame, point, u, v),
-    counts, maps, M, cams) for windows of n cameras, and the problems they
-    stand for (as test_ba_fixed._stage_inputs)."""
-    W = len(wins)
-    cap = max(-(-len(w[2]) // n) for w in wins)
-    rows = np.zeros((W * n, cap, 4))
-    cnt = np.zeros(W * n, np.int32)
-    maps = np.zeros((W, max(len(w[1]) for w in wins), 3))
-    M = np.zeros(W, np.int32)
-    cams = np.zeros((W * n, 9))
-    probs = []
-    for w, (c0, p0, ci, pi, qs) in enumerate(wins):
-        maps[w, :len(p0)] = p0
-        M[w] = len(p0)
-        cams[w * n:(w + 1) * n] = c0
-        qq = []
-        for j, idx in enumerate(np.array_split(np.arange(len(ci)), n)):
-            b = w * n + j
-            cnt[b] = len(idx)
-            rows[b, :len(idx)] = np.stack([ci[idx], pi[idx], qs[idx, 0] + u_off, qs[idx, 1] + v_off], 1)
-            qq.append(np.stack([rows[b, :len(idx), 2] - u_off, rows[b, :len(idx), 3] - v_off], 1))
-        probs.append((c0, p0, ci, pi, np.concatenate(qq)))
-    return (rows, cnt, maps, M, cams, u_off, v_off), probs
-
-
 @pytest.mark.gpu
 def test_gpu_window_set_stage_loss_equals_separate_problems():
     """BAWindowSet.stage(loss="cauchy"): the natively staged descriptors (which
@@ -603,7 +578,7 @@ def test_gpu_window_set_stage_loss_equals_separate_problems():
     import torch
     from slam355 import ba
 
-    inp, probs = _stage_inputs([outlier_case(6, 150, 4), outlier_case(6, 150, 1)], 6)
+    inp, probs = stage_inputs([outlier_case(6, 150, 4), outlier_case(6, 150, 1)], 6)
     s = torch.cuda.Stream()
     ws = ba.BAWindowSet()
     for kw in (dict(loss="cauchy", f_scale=DELTA), dict()):
