@@ -351,6 +351,83 @@ int slam_track_rows(const int32_t* d_idx2, const uint8_t* d_good, const int32_t*
                     double* d_rows, int32_t* d_count, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Robust pose refinement from track rows (motion-only bundle adjustment, the
+ * pose optimisation that follows search by projection): start at the
+ * predicted pose, minimise the robust reprojection error of the matched
+ * landmarks, drop the matches that do not fit, repeat, and return the pose
+ * with its information matrix.  Batched, asynchronous on `stream`; no
+ * allocation, no workspace, no host synchronisation.
+ *
+ * Inputs.  d_rows [batch][rows_cap][4] f64 and d_count [batch] i32 (clamped to
+ * [0, rows_cap]) as slam_track_rows writes them (frame, landmark, x, y; the
+ * frame column is not read); d_X [n_x][3] f64 the map; d_poses [batch][16] f64
+ * row-major camera-to-world as in slam_project_landmarks; d_P [12] f64 a 3x4
+ * projection whose fourth column may be non-zero.
+ *
+ * Frame.  R, t from the input pose.  Observation k < count has landmark l and
+ * pixel (x, y); with l outside [0, n_x) (NaN included) it is never valid.
+ * Q_k = R^T (X_l - t) in the operation order of slam_project_landmarks.
+ *
+ * Parameters.  A left increment p = (w, v), starting at 0:
+ *   X_cam = Rod(w) Q_k + v          (Rod: cv::Rodrigues; identity below |w| = 2^-52)
+ *   h     = P[:, :3] X_cam + P[:, 3]
+ *   r     = (h0 (1 / h2) - x, h1 (1 / h2) - y)
+ * and the observation is VALID AT p iff X_cam[2] > min_depth and h2 > 0.  No
+ * matrix logarithm is taken anywhere: an input pose with a rotation near pi is
+ * as good as any other.  The 2x6 Jacobian is d(u, v)/dX_cam (for the general
+ * P: ((P[0,:3] - u P[2,:3]) / h2, (P[1,:3] - v P[2,:3]) / h2)) times
+ * [d(Rod(w) Q)/dw | I], the rotation block in the Gallego-Yezzi form
+ * -R [Q]x (w w^T + (R^T - I) [w]x) / |w|^2, and -[R Q]x when |w|^2 < 1e-24.
+ *
+ * One round, over a fixed active set A: `iters` Levenberg-Marquardt iterations
+ * with lambda starting at 1e-3.  H = sum J^T J, g = sum J^T r, cost = sum term
+ * over A, where for loss 0 (linear) term = |r|^2, and for loss 1 huber,
+ * 2 soft_l1, 3 cauchy (delta = loss_scale; the losses of slam_ba_problem) r and
+ * J are scaled by sqrt(rho'(z)), z = |r|^2 / delta^2, and term = delta^2 rho(z).
+ * The step solves (H + lambda max(diag H, 1e-12)) d = -g by Cholesky; the
+ * trial p + d is accepted iff the factorisation succeeded, every observation
+ * of A is valid at the trial and cost_trial < cost; lambda <- max(lambda / 10,
+ * 1e-12) on accept, min(10 lambda, 1e12) on reject.
+ *
+ * Rounds.  A_0 = the observations valid at p = 0.  After each of the n_rounds
+ * rounds EVERY observation is classified, not only those of A: it is an
+ * inlier iff it is valid at p and its unweighted |r|^2 <= gate^2, and the next
+ * round's A is the inliers -- an observation rejected in one round can come
+ * back in the next.  Fewer than min_inliers inliers after a round: status 2.
+ *
+ * Outputs (d_poses_out may not alias d_poses).
+ *   d_poses_out [batch][16]  R' = R Rod(w)^T, t' = t - R' v, last row 0 0 0 1
+ *   d_mask [batch][rows_cap] u8  the last classification made (status 1: the
+ *                            observations valid at the input pose); entries
+ *                            >= count are not written
+ *   d_ninl [batch] i32       the number of ones in it
+ *   d_cost [batch] f64       sum of term over the final inliers at the final pose
+ *   d_info [batch][36] f64   row-major, symmetric bit for bit: sum J~^T J~ over
+ *                            the final inliers relinearised at the returned
+ *                            pose (p = 0, Q <- X_cam, hence the -[X_cam]x
+ *                            branch), J~ robust-weighted: the information of the
+ *                            perturbation X_cam <- Exp(dw) X_cam + dv in the
+ *                            order (dw, dv)
+ *   d_status [batch] i32     0 ok; 1 fewer than min_inliers observations valid
+ *                            at the input pose (nothing is optimised); 2 the
+ *                            inliers fell below min_inliers after a round.
+ * For status 1 and 2 d_poses_out is the input pose bit for bit, d_info and
+ * d_cost are zeros and d_ninl is -1.
+ *
+ * Sums are formed per lane, per wave and then in wave order, so results equal
+ * a sequential evaluation up to the rounding of the summation order only.
+ * SLAM_ERR_ARG before any GPU call: a null pointer; batch or rows_cap outside
+ * 1..65535; n_x < 0; n_rounds outside 1..8; iters outside 1..50; min_inliers
+ * < 3; loss outside 0..3; loss_scale <= 0 with loss != 0; gate <= 0;
+ * min_depth NaN. */
+int slam_pose_refine(const double* d_rows, const int32_t* d_count, int rows_cap, int batch,
+                     const double* d_X, int n_x, const double* d_poses, const double* d_P,
+                     int loss, double loss_scale, double gate, double min_depth,
+                     int n_rounds, int iters, int min_inliers,
+                     double* d_poses_out, uint8_t* d_mask, int32_t* d_ninl, int32_t* d_status,
+                     double* d_info, double* d_cost, void* stream);
+
+/* ------------------------------------------------------------------------
  * Tiled ORB detector + rBRIEF descriptor.
  *
  * Replaces orb_detector_using_tiles (/root/reference/orb.py:4-25), i.e. the

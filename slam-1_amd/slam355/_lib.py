@@ -117,6 +117,8 @@ SIGNATURES = {
                                  c_p],
     "slam_match_unique": [c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_p, c_p, c_p],
     "slam_track_rows": [c_p, c_p, c_p, c_int, c_p, c_int, c_int, c_int, c_int, c_p, c_p, c_p],
+    "slam_pose_refine": [c_p, c_p, c_int, c_int, c_p, c_int, c_p, c_p, c_int, c_double, c_double,
+                         c_double, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     "slam_fundamental_lmeds": [c_p, c_p, c_p, c_int, c_int, c_uint64, c_int, c_int, c_p, c_p, c_p,
                                c_p],
     "slam_fundamental_lmeds_ws": [c_p, c_p, c_p, c_int, c_int, c_uint64, c_int, c_int, c_p, c_p,

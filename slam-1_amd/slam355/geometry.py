@@ -111,6 +111,51 @@ def project_landmarks(X, nx, poses, P, W, H, margin=0.0, min_depth=0.1, out=None
     return uv, z
 
 
+REFINE_LOSSES = {"linear": 0, "huber": 1, "soft_l1": 2, "cauchy": 3}
+
+
+def refine_pose(rows, count, X, n_x, poses, P, *, loss="huber", loss_scale=2.4477, gate=2.4477,
+                rounds=4, iters=10, min_inliers=10, min_depth=0.1, out=None, stream=None):
+    """Robust pose refinement from track rows (slam_pose_refine; motion-only BA).
+
+    rows [B,rows_cap,4] f64 and count [B] i32 as track_rows / LandmarkMap.observe
+    return them, X [cap,3] f64 the map with its first n_x rows in use, poses
+    [B,4,4] f64 camera-to-world (predicted), P 3x4 -> (poses [B,4,4] f64, mask
+    [B,rows_cap] u8, ninl [B] i32, status [B] i32, info [B,6,6] f64, cost [B]
+    f64).  status 0 ok, 1 too few valid observations, 2 too few inliers (1, 2:
+    the input pose comes back, ninl -1).  The defaults 2.4477 = sqrt(5.991) are
+    the 95 % chi-square bound of 2 degrees of freedom at sigma = 1 px.  `out`:
+    the six outputs preallocated (poses may not be the input tensor)."""
+    B, rows_cap = int(rows.shape[0]), int(rows.shape[1])
+    dev = rows.device
+    if loss not in REFINE_LOSSES:
+        raise ValueError(f"refine_pose: loss {loss!r} is not one of {sorted(REFINE_LOSSES)}")
+    n_x = int(n_x)
+    if tuple(rows.shape) != (B, rows_cap, 4) or tuple(poses.shape) != (B, 4, 4) or \
+            int(count.shape[0]) != B:
+        raise ValueError("refine_pose: rows [B,cap,4], count [B] and poses [B,4,4] do not agree")
+    if X.dim() != 2 or int(X.shape[1]) != 3 or not 0 <= n_x <= int(X.shape[0]):
+        raise ValueError("refine_pose: X must be [cap,3] with 0 <= n_x <= cap")
+    Pd = P if isinstance(P, torch.Tensor) else torch.as_tensor(np.asarray(P, np.float64),
+                                                               device=dev)
+    if out is None:
+        po = torch.zeros((B, 4, 4), dtype=torch.float64, device=dev)
+        mask = torch.zeros((B, rows_cap), dtype=torch.uint8, device=dev)
+        ninl = torch.zeros((B,), dtype=torch.int32, device=dev)
+        status = torch.zeros((B,), dtype=torch.int32, device=dev)
+        info = torch.zeros((B, 6, 6), dtype=torch.float64, device=dev)
+        cost = torch.zeros((B,), dtype=torch.float64, device=dev)
+    else:
+        po, mask, ninl, status, info, cost = out
+        if po.data_ptr() == poses.data_ptr():
+            raise ValueError("refine_pose: the output poses may not alias the input")
+    _lib.call("slam_pose_refine", ptr(rows), ptr(count), rows_cap, B, ptr(X), n_x, ptr(poses),
+              ptr(Pd), REFINE_LOSSES[loss], float(loss_scale), float(gate), float(min_depth),
+              int(rounds), int(iters), int(min_inliers), ptr(po), ptr(mask), ptr(ninl), ptr(status),
+              ptr(info), ptr(cost), stream_ptr(stream))
+    return po, mask, ninl, status, info, cost
+
+
 def triangulate(ptl, ptr_, count, P_l, P_r, out=None, stream=None):
     """ptl/ptr [B,cap,2] f64, P 3x4 (shared) or [B,3,4] -> X [B,cap,3] f64."""
     B, cap, _ = ptl.shape

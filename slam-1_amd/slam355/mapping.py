@@ -11,6 +11,9 @@ the host only tracks an upper bound of M to size grids and grow the buffer.
 by projection: project the map with the predicted pose, search each landmark's
 descriptor among the keypoints in a window round its predicted pixel
 (slam_project_landmarks ... slam_track_rows; no counterpart in the reference).
+`LandmarkMap.localize` turns the matches back into poses: robust motion-only
+refinement from the predicted pose (slam_pose_refine), twice, the second time
+on a narrower search at the refined pose.
 """
 from __future__ import annotations
 
@@ -104,9 +107,12 @@ class LandmarkMap:
         self.X = torch.zeros((self.cap, 3), dtype=torch.float64, device=self.dev)
         self.desc = torch.zeros((self.cap, 32), dtype=torch.uint8, device=self.dev)
         self.n = 0
+        self.rows_cap = max(min(self.cap, self.kp_cap), 1)   # track rows of one frame
         self._bufs = {}      # batch size -> the device buffers of observe
+        self._rbufs = {}     # batch size -> the device buffers of localize
         self._tracks = []    # (rows, count) of every observe call
         self.uv = self.z = self.idx2 = self.dist2 = self.good = self.owner = None
+        self.first = self.cost = None
 
     def add(self, X, desc):
         """Append landmarks: X [k,3] f64, desc [k,32] u8 (host arrays or tensors)."""
@@ -149,6 +155,12 @@ class LandmarkMap:
         f64, count [B] i32) on the device.  `uv`, `z`, `idx2`, `dist2`, `good`
         (after the uniqueness pass) and `owner` stay as attributes; they are
         overwritten by the next call of the same batch size."""
+        return self._observe(frame0, poses, kp, desc, n_kp, radius, max_dist, ratio, margin,
+                             min_depth, stream)
+
+    def _observe(self, frame0, poses, kp, desc, n_kp, radius, max_dist, ratio, margin, min_depth,
+                 stream, out=None):
+        """observe; with out = (rows, count) it writes there and keeps nothing for tracks()."""
         B = int(poses.shape[0])
         if tuple(kp.shape) != (B, self.kp_cap, 5) or tuple(desc.shape) != (B, self.kp_cap, 32):
             raise ValueError("LandmarkMap.observe: kp / desc do not match (B, kp_cap)")
@@ -165,14 +177,64 @@ class LandmarkMap:
                 ratio=ratio, out=(b["idx2"], b["dist2"], b["good0"]))
             owner, good = matcher.unique_matches(idx2, dist2, good0, b["nq"], self.kp_cap,
                                                  out=(b["owner"], b["good"]))
-            # fresh outputs per call: the caller keeps them while later frames run
-            rows = torch.zeros((B, max(min(self.cap, self.kp_cap), 1), 4), dtype=torch.float64,
-                               device=self.dev)
-            count = torch.zeros((B,), dtype=torch.int32, device=self.dev)
+            if out is None:
+                # fresh outputs per call: the caller keeps them while later frames run
+                rows = torch.zeros((B, self.rows_cap, 4), dtype=torch.float64, device=self.dev)
+                count = torch.zeros((B,), dtype=torch.int32, device=self.dev)
+            else:
+                rows, count = out
             matcher.track_rows(idx2, good, b["nq"], kp, frame0, out=(rows, count))
         self.uv, self.z, self.idx2, self.dist2, self.good, self.owner = uv, z, idx2, dist2, good, owner
-        self._tracks.append((rows, count))
+        if out is None:
+            self._tracks.append((rows, count))
         return rows, count
+
+    def _refine_buffers(self, B):
+        b = self._rbufs.get(B)
+        if b is None:
+            f64 = dict(dtype=torch.float64, device=self.dev)
+            i32 = dict(dtype=torch.int32, device=self.dev)
+
+            def outs():  # the six outputs of geometry.refine_pose
+                return (torch.zeros((B, 4, 4), **f64),
+                        torch.zeros((B, self.rows_cap), dtype=torch.uint8, device=self.dev),
+                        torch.zeros((B,), **i32), torch.zeros((B,), **i32),
+                        torch.zeros((B, 6, 6), **f64), torch.zeros((B,), **f64))
+            b = dict(rows=torch.zeros((B, self.rows_cap, 4), **f64), count=torch.zeros((B,), **i32),
+                     first=outs(), second=outs())
+            self._rbufs[B] = b
+        return b
+
+    def localize(self, frame0, poses, kp, desc, n_kp, radius=(15.0, 5.0), max_dist=64,
+                 ratio=(7, 10), margin=0.0, min_depth=0.1, stream=None, **refine_options):
+        """Track the map from predicted poses: observe with radius[0] and refine the
+        poses on those matches (geometry.refine_pose, its options in
+        `refine_options`), then observe again with radius[1] at the refined poses
+        and refine once more.  A frame whose first refinement fails (status != 0)
+        keeps its predicted pose for the second pass.  Only the second pass's rows
+        are kept for `tracks()`.
+
+        -> (poses [B,4,4] f64, rows, count, mask [B,rows_cap] u8, ninl [B] i32,
+        status [B] i32, info [B,6,6] f64), the last four of the second
+        refinement.  rows and count are fresh tensors as observe returns them;
+        the others are per-batch-size buffers, overwritten by the next call of
+        the same batch size, as are `first` (the six outputs of the first
+        refinement) and `cost`.  One stream, no host synchronisation: after a
+        first call has allocated the buffers it can be captured in a graph."""
+        B = int(poses.shape[0])
+        b = self._refine_buffers(B)
+        obs = (max_dist, ratio, margin, min_depth, stream)
+        with torch.cuda.stream(stream):
+            rows, count = self._observe(frame0, poses, kp, desc, n_kp, radius[0], *obs,
+                                        out=(b["rows"], b["count"]))
+            first = geometry.refine_pose(rows, count, self.X, self.n, poses, self.P,
+                                         min_depth=min_depth, out=b["first"], **refine_options)
+            rows, count = self._observe(frame0, first[0], kp, desc, n_kp, radius[1], *obs)
+            po, mask, ninl, status, info, cost = geometry.refine_pose(
+                rows, count, self.X, self.n, first[0], self.P, min_depth=min_depth,
+                out=b["second"], **refine_options)
+        self.first, self.cost = first, cost
+        return po, rows, count, mask, ninl, status, info
 
     def reset_tracks(self):
         """Forget the rows kept for `tracks()` (the landmarks stay)."""
