@@ -2,9 +2,11 @@
 export (XXXport_files.py:16-92): oracle + host mirror pinned to goldens made by
 running the reference itself (tests/golden/make_goldens.py), GPU parity.
 
-Association bar: bit-exact rows and map (indices, copied coordinates).  The
-nearest-neighbour tie rule (lowest index) is unpinned against KDTree, which
-leaves exact ties unspecified; the goldens contain none.
+Association bar: bit-exact rows and map (indices, copied coordinates).  KDTree
+leaves exact nearest-neighbour ties unspecified and the goldens contain none;
+the device's rule (lowest index, inside a chunk and across chunk partials), the
+gate at equality and the chunk / tile boundaries are pinned by test_map_ties.py
+against a brute-force reference on a lattice where ties are exact.
 """
 import os
 import tempfile

@@ -238,6 +238,8 @@ def test_gpu_tracked_frames_feed_local_ba(request, B):
     from slam355.ba import BAProblem
     from slam355.pipeline import LocalMap, Tracker
 
+    import shapes_ref as sr
+
     L, R, poses, rig = request.getfixturevalue("corridor" if B == 3 else "corridor9")
     trk = Tracker(B, 720, 1280, rig.P_l, rig.P_r, max_kp_per_tile=64, seed=6)
     lm = LocalMap(trk)
@@ -247,7 +249,7 @@ def test_gpu_tracked_frames_feed_local_ba(request, B):
     # oracle chain (main.py:79-127)
     cache = {}
     Qs = np.empty((0, 3))
-    om_rows = []
+    om_rows, bf_rows = [], []
     pose, T = np.eye(4), np.eye(4)
     frames = [np.eye(4)]
     t_cnt = trk.t_cnt.cpu().numpy()
@@ -271,10 +273,17 @@ def test_gpu_tracked_frames_feed_local_ba(request, B):
         # landmark of a map that holds near-duplicate points, and the gate) is
         # exact given its inputs, but a near-tie can flip under the 1e-9-level
         # differences of the upstream triangulation, so it is checked on them
+        Qs_in = Qs
         Qs, rows = omap.append_keypoints(Qs, d_abs[i, :n], 0.01, d_q1[i, :n], i, d_Q1[i, :n])
         om_rows.append(rows)
+        # and the same frame by brute force with the first index on ties (the
+        # device's rule, pinned by test_map_ties.py): the same map, every index
+        bQs, brows = sr.map_assoc(Qs_in, d_abs[i, :n], 0.01, d_q1[i, :n], i, d_Q1[i, :n])
+        assert np.array_equal(bQs, Qs), i
+        bf_rows.append(brows)
     om = np.vstack(om_rows)
     got = lm.optimization_matrix()
+    assert np.array_equal(got, np.vstack(bf_rows))  # every index, ties included
     assert got.shape == om.shape
     assert np.array_equal(got[:, [0, 2, 3]], om[:, [0, 2, 3]])
     gQ = lm.store.points().cpu().numpy()
