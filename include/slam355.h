@@ -428,6 +428,119 @@ int slam_pose_refine(const double* d_rows, const int32_t* d_count, int rows_cap,
                      double* d_info, double* d_cost, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Landmark life cycle: what a map does after a batch of frames was tracked --
+ * count how often each landmark was in view and how often it was found, make
+ * new landmarks from the triangulated keypoints no landmark claimed, drop the
+ * landmarks that do not hold up, and now and then squeeze the dropped ones
+ * out.  Every call is asynchronous on `stream`, allocates nothing and never
+ * synchronises; SLAM_ERR_ARG (a null pointer is reported by the argument's
+ * name) comes before any GPU call.
+ *
+ * Landmark state.  Beside d_X [x_cap][3] f64 and d_desc [x_cap][32] u8 (16-byte
+ * aligned) a landmark has four i32 fields: d_visible (frames it was predicted
+ * in view), d_found (frames it was matched in), d_born and d_last (the frames
+ * of its first and latest observation).  The count *d_n is a DEVICE i32,
+ * clamped to [0, x_cap] wherever it is read.  Landmark i < *d_n is DEAD iff
+ * d_X[i][0] is NaN: a dead landmark never projects (xc2 > min_depth is false)
+ * and is never valid in slam_pose_refine, so indices stay stable and earlier
+ * track rows keep their meaning.  1 <= x_cap <= 1 << 20.
+ *
+ * 1. Score.  d_uv [batch][x_cap][2] f32, d_good [batch][x_cap] u8 and d_nq
+ *    [batch] i32 as ONE run of steps 1-4 of guided matching left them; nq_b
+ *    (clamped to [0, x_cap]) is the count that run used, not the current *d_n,
+ *    and entries >= nq_b are stale: they are not used.  For every i < x_cap
+ *      visible[i] += #{b : i < nq_b, uv[b][i][0] finite}
+ *      found[i]   += #{b : i < nq_b, good[b][i] != 0}
+ *      last[i]     = max(last[i], frame0 + b) over the b counted in found.
+ *    One lane per landmark, a loop over the batch: exact, no atomics.
+ *    1 <= batch <= 65535. */
+int slam_map_score(const float* d_uv, const uint8_t* d_good, const int32_t* d_nq, int x_cap,
+                   int batch, int frame0, int32_t* d_visible, int32_t* d_found, int32_t* d_last,
+                   void* stream);
+
+/* 2. Spawn.  d_Xc [batch][p_cap][3] f64 camera-frame points as
+ *    slam_triangulate writes them, d_pairs [batch][p_cap][2] i32 whose column 0
+ *    is the keypoint index j, d_count [batch] (clamped to [0, p_cap]); d_kp
+ *    [batch][kp_cap][5] f32, d_kp_desc [batch][kp_cap][32] u8 (16-byte aligned),
+ *    d_nkp [batch] (clamped as in slam_kp_grid); d_owner [batch][kp_cap] i32, the
+ *    output of slam_match_unique, read and updated; d_poses [batch][16] f64
+ *    camera-to-world (R its 3x3, t its last column); d_spawn [batch] u8, the
+ *    frames that may spawn.  Entry (b, k) is a CANDIDATE iff
+ *      spawn[b] != 0 and k < count_b,
+ *      0 <= j < nkp_b and owner[b][j] == -1,
+ *      xc0, xc1, xc2 are finite and z_min < xc2 < z_max (both ends excluded),
+ *      no k' < k of the same frame is a candidate with the same j.
+ *    Candidates are numbered in order of b, then k; number r gets landmark
+ *    i = n0 + r, n0 = *d_n on entry, and is ACCEPTED iff i < x_cap.  For an
+ *    accepted candidate, without contraction and left to right,
+ *      X[i][c] = R[c][0] xc0 + R[c][1] xc1 + R[c][2] xc2 + t[c]
+ *      desc[i] = d_kp_desc[b][j], visible[i] = found[i] = 1,
+ *      born[i] = last[i] = frame0 + b, owner[b][j] = i,
+ *    and the row [frame0 + b, i, (double)kx_j, (double)ky_j] is appended to
+ *    d_rows[b] ([batch][rows_cap][4] f64) at d_rows_count[b] (clamped to [0,
+ *    rows_cap]), which grows by the frame's accepted candidates: new indices
+ *    exceed all old ones, so rows written by slam_track_rows stay in ascending
+ *    landmark order.  rows_cap >= min(x_cap, kp_cap), so rows that hold one
+ *    row per owned keypoint cannot overflow (a row past rows_cap is not
+ *    written).  Further outputs: *d_n = min(n0 + candidates, x_cap), d_spawned
+ *    [batch] i32 the accepted candidates per frame, *d_dropped i32 the
+ *    candidates not accepted.
+ *    d_ws: slam_map_spawn_workspace_bytes(batch, kp_cap) bytes, 4-byte aligned,
+ *    contents irrelevant on entry.  Two launches of one workgroup per frame:
+ *    the first races k into a claim word per keypoint (integer atomicMin: the
+ *    lowest k wins whatever the arrival order) and counts the frame's
+ *    candidates; the second adds up the counts of the frames before its own
+ *    and scatters.  1 <= batch <= 1024, 1 <= p_cap <= 1 << 20, 1 <= kp_cap <=
+ *    65535; z_min < z_max (NaN refused). */
+int slam_map_spawn_workspace_bytes(int batch, int kp_cap, size_t* bytes);
+int slam_map_spawn(const double* d_Xc, const int32_t* d_pairs, const int32_t* d_count, int p_cap,
+                   const float* d_kp, const uint8_t* d_kp_desc, const int32_t* d_nkp, int kp_cap,
+                   int32_t* d_owner, const double* d_poses, const uint8_t* d_spawn, int batch,
+                   double z_min, double z_max, int frame0, double* d_X, uint8_t* d_desc,
+                   int32_t* d_visible, int32_t* d_found, int32_t* d_born, int32_t* d_last,
+                   int32_t* d_n, int x_cap, double* d_rows, int32_t* d_rows_count, int rows_cap,
+                   int32_t* d_spawned, int32_t* d_dropped, void* d_ws, size_t ws_size,
+                   void* stream);
+
+/* 3. Cull.  A live landmark i < *d_n dies iff (products and the difference in
+ *    64 bits)
+ *      visible[i] >= min_visible and ratio_den found[i] < ratio_num visible[i], or
+ *      now - born[i] >= age and found[i] < min_found.
+ *    Dying writes NaN to all three of d_X[i]; dead landmarks are left alone;
+ *    *d_nculled i32 = the number that died in this call (zeroed on the stream,
+ *    then an integer atomic add).  ratio_num >= 0, ratio_den >= 1. */
+int slam_map_cull(double* d_X, const int32_t* d_visible, const int32_t* d_found,
+                  const int32_t* d_born, const int32_t* d_n, int x_cap, int now, int min_visible,
+                  int ratio_num, int ratio_den, int age, int min_found, int32_t* d_nculled,
+                  void* stream);
+
+/* 4. Compact.  STABLE compaction of the live landmarks of [0, *d_n): landmark
+ *    i goes to d_remap[i] = the number of live landmarks below it, all six
+ *    arrays copied into the *_out arrays (same shapes; an output may not be
+ *    its own input).  d_remap [x_cap] i32 is -1 for a dead landmark and for
+ *    every i >= *d_n; *d_n_out i32 = the new count (not d_n: the last launch
+ *    still reads it).
+ *    Blocks of 1024 landmarks count, one workgroup scans the block counts,
+ *    the blocks scatter: three launches, no workgroup waits for another (the
+ *    block counts live in d_remap between the launches). */
+int slam_map_compact(const double* d_X, const uint8_t* d_desc, const int32_t* d_visible,
+                     const int32_t* d_found, const int32_t* d_born, const int32_t* d_last,
+                     const int32_t* d_n, int x_cap, double* d_X_out, uint8_t* d_desc_out,
+                     int32_t* d_visible_out, int32_t* d_found_out, int32_t* d_born_out,
+                     int32_t* d_last_out, int32_t* d_remap, int32_t* d_n_out, void* stream);
+
+/*    Track rows after a compaction.  d_rows [batch][rows_cap][4] f64 and
+ *    d_count [batch] i32 (clamped to [0, rows_cap]) in the format of
+ *    slam_track_rows.  A row whose landmark value v is not in (-1, x_cap), NaN
+ *    included, or whose d_remap[(int)v] is -1 is dropped; the others are
+ *    written to d_rows_out (not d_rows) in their order with d_remap[(int)v] as
+ *    the landmark, and d_count_out [batch] counts them.  1 <= batch, rows_cap
+ *    <= 65535. */
+int slam_rows_remap(const double* d_rows, const int32_t* d_count, int rows_cap, int batch,
+                    const int32_t* d_remap, int x_cap, double* d_rows_out, int32_t* d_count_out,
+                    void* stream);
+
+/* ------------------------------------------------------------------------
  * Tiled ORB detector + rBRIEF descriptor.
  *
  * Replaces orb_detector_using_tiles (/root/reference/orb.py:4-25), i.e. the

@@ -119,6 +119,15 @@ SIGNATURES = {
     "slam_track_rows": [c_p, c_p, c_p, c_int, c_p, c_int, c_int, c_int, c_int, c_p, c_p, c_p],
     "slam_pose_refine": [c_p, c_p, c_int, c_int, c_p, c_int, c_p, c_p, c_int, c_double, c_double,
                          c_double, c_int, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
+    "slam_map_score": [c_p, c_p, c_p, c_int, c_int, c_int, c_p, c_p, c_p, c_p],
+    "slam_map_spawn_workspace_bytes": [c_int, c_int, ctypes.POINTER(c_size_t)],
+    "slam_map_spawn": [c_p, c_p, c_p, c_int, c_p, c_p, c_p, c_int, c_p, c_p, c_p, c_int, c_double,
+                       c_double, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_p, c_p, c_int,
+                       c_p, c_p, c_p, c_size_t, c_p],
+    "slam_map_cull": [c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_p,
+                      c_p],
+    "slam_map_compact": [c_p] * 7 + [c_int] + [c_p] * 9,
+    "slam_rows_remap": [c_p, c_p, c_int, c_int, c_p, c_int, c_p, c_p, c_p],
     "slam_fundamental_lmeds": [c_p, c_p, c_p, c_int, c_int, c_uint64, c_int, c_int, c_p, c_p, c_p,
                                c_p],
     "slam_fundamental_lmeds_ws": [c_p, c_p, c_p, c_int, c_int, c_uint64, c_int, c_int, c_p, c_p,

@@ -13,7 +13,10 @@ descriptor among the keypoints in a window round its predicted pixel
 (slam_project_landmarks ... slam_track_rows; no counterpart in the reference).
 `LandmarkMap.localize` turns the matches back into poses: robust motion-only
 refinement from the predicted pose (slam_pose_refine), twice, the second time
-on a narrower search at the refined pose.
+on a narrower search at the refined pose.  `score`, `spawn`, `cull` and
+`compact` let the map follow the camera (slam_map_score ... slam_map_compact):
+the landmark count lives on the device, so `step` -- localize, score, spawn
+from the keyframes, cull -- runs a batch of frames without a synchronisation.
 """
 from __future__ import annotations
 
@@ -91,7 +94,12 @@ class LandmarkMap:
     """Landmarks with descriptors, matched to new frames by projection.
 
     X [capacity,3] f64 world points and desc [capacity,32] u8 live on the
-    device; `add` appends (sizes known on the host).  `observe` projects the
+    device, with visible / found / born / last [capacity] i32 and the count
+    `n_dev` (int32 [1]) beside them; `add` appends (sizes known on the host),
+    `spawn` appends on the device.  `n` is the count on the host: exact while
+    only `add` and `compact` change the map, an upper bound after a `spawn`
+    until `size()` reads `n_dev`.  A landmark that `cull` dropped keeps its
+    index with a NaN position until `compact`.  `observe` projects the
     map into a batch of frames with their predicted poses, searches every
     landmark's descriptor among the keypoints within `radius` pixels of its
     predicted position, gives each keypoint to at most one landmark and returns
@@ -106,7 +114,15 @@ class LandmarkMap:
         self.P = to_dev(np.ascontiguousarray(P, np.float64).reshape(3, 4))
         self.X = torch.zeros((self.cap, 3), dtype=torch.float64, device=self.dev)
         self.desc = torch.zeros((self.cap, 32), dtype=torch.uint8, device=self.dev)
+        self.visible, self.found, self.born, self.last = (
+            torch.zeros((self.cap,), dtype=torch.int32, device=self.dev) for _ in range(4))
         self.n = 0
+        self.n_dev = torch.zeros((1,), dtype=torch.int32, device=self.dev)
+        self._exact = True   # n == n_dev (False between a spawn and the next size())
+        self._alt = None     # the other half of compact's ping-pong buffers
+        self._life = {}      # batch size -> the device buffers of spawn
+        self._nq = None      # the nq of the last observe
+        self.remap = self.nculled = self.spawned = self.dropped = None
         self.rows_cap = max(min(self.cap, self.kp_cap), 1)   # track rows of one frame
         self._bufs = {}      # batch size -> the device buffers of observe
         self._rbufs = {}     # batch size -> the device buffers of localize
@@ -114,19 +130,35 @@ class LandmarkMap:
         self.uv = self.z = self.idx2 = self.dist2 = self.good = self.owner = None
         self.first = self.cost = None
 
-    def add(self, X, desc):
-        """Append landmarks: X [k,3] f64, desc [k,32] u8 (host arrays or tensors)."""
+    def add(self, X, desc, frame=0):
+        """Append landmarks: X [k,3] f64, desc [k,32] u8 (host arrays or tensors),
+        first seen in `frame` (visible = found = 1, born = last = frame, what
+        `spawn` gives a new landmark).  After a `spawn` it synchronises (`size`)."""
         X = to_dev(X, torch.float64).reshape(-1, 3)
         desc = to_dev(desc, torch.uint8).reshape(-1, 32)
         k = int(X.shape[0])
         if int(desc.shape[0]) != k:
             raise ValueError("LandmarkMap.add: X and desc differ in length")
-        if self.n + k > self.cap:
-            raise ValueError(f"LandmarkMap.add: capacity {self.cap} < {self.n} + {k}")
-        self.X[self.n:self.n + k] = X
-        self.desc[self.n:self.n + k] = desc
-        self.n += k
+        n = self.size()
+        if n + k > self.cap:
+            raise ValueError(f"LandmarkMap.add: capacity {self.cap} < {n} + {k}")
+        self.X[n:n + k] = X
+        self.desc[n:n + k] = desc
+        self.visible[n:n + k] = 1
+        self.found[n:n + k] = 1
+        self.born[n:n + k] = int(frame)
+        self.last[n:n + k] = int(frame)
+        self.n = n + k
+        self.n_dev.fill_(self.n)
         return self
+
+    def size(self) -> int:
+        """The number of landmark slots in use, dead ones included.  Synchronises
+        after a `spawn`; otherwise the host already knows it."""
+        if not self._exact:
+            self.n = int(self.n_dev.item())
+            self._exact = True
+        return self.n
 
     def _buffers(self, B):
         b = self._bufs.get(B)
@@ -166,7 +198,7 @@ class LandmarkMap:
             raise ValueError("LandmarkMap.observe: kp / desc do not match (B, kp_cap)")
         b = self._buffers(B)
         with torch.cuda.stream(stream):  # the fills below follow the current stream
-            b["nq"].fill_(self.n)
+            b["nq"].copy_(self.n_dev.expand(B))
             b["qr"].fill_(float(radius))
             uv, z = geometry.project_landmarks(self.X, b["nq"], poses, self.P, self.W, self.H,
                                                margin=margin, min_depth=min_depth,
@@ -185,6 +217,7 @@ class LandmarkMap:
                 rows, count = out
             matcher.track_rows(idx2, good, b["nq"], kp, frame0, out=(rows, count))
         self.uv, self.z, self.idx2, self.dist2, self.good, self.owner = uv, z, idx2, dist2, good, owner
+        self._nq = b["nq"]
         if out is None:
             self._tracks.append((rows, count))
         return rows, count
@@ -240,10 +273,134 @@ class LandmarkMap:
         """Forget the rows kept for `tracks()` (the landmarks stay)."""
         self._tracks = []
 
-    def tracks(self, compact=False):
+    # ------------------------------------------------------------ life cycle
+    def _fields(self):
+        return self.X, self.desc, self.visible, self.found, self.born, self.last
+
+    def score(self, frame0, stream=None):
+        """Count the last `observe` (in `localize`: its second pass) into visible /
+        found / last: slam_map_score on the uv, good and nq that call left."""
+        if self.uv is None:
+            raise ValueError("LandmarkMap.score: no observe call to score")
+        _lib.call("slam_map_score", ptr(self.uv), ptr(self.good), ptr(self._nq), self.cap,
+                  int(self.uv.shape[0]), int(frame0), ptr(self.visible), ptr(self.found),
+                  ptr(self.last), stream_ptr(stream))
+
+    def _life_buffers(self, B):
+        b = self._life.get(B)
+        if b is None:
+            nb = ctypes.c_size_t(0)
+            _lib.call("slam_map_spawn_workspace_bytes", B, self.kp_cap, ctypes.byref(nb))
+            b = dict(ws=torch.empty(int(nb.value), dtype=torch.uint8, device=self.dev),
+                     spawned=torch.zeros((B,), dtype=torch.int32, device=self.dev),
+                     dropped=torch.zeros((1,), dtype=torch.int32, device=self.dev))
+            self._life[B] = b
+        return b
+
+    def spawn(self, frame0, poses, Xc, pairs, count, kp, desc, n_kp, keyframe,
+              z_range=(0.1, 70.0), rows=None, rows_count=None, stream=None):
+        """New landmarks from the triangulated keypoints no landmark owns
+        (slam_map_spawn): Xc [B,p_cap,3] f64 camera-frame points, pairs
+        [B,p_cap,2] i32 (column 0 the keypoint) and count [B] i32 as
+        Tracker.track leaves X, f_pairs and f_cnt; kp, desc, n_kp the frames'
+        keypoints; poses [B,4,4] camera-to-world; keyframe [B] u8, the frames that
+        may spawn; z_range the accepted depth (70 m: the reference's
+        close_def_in_m).  It reads and updates the `owner` of the last observe and
+        appends the new landmarks' rows to `rows` / `rows_count`, by default the
+        tensors that observe returned, so the spawning observation is in
+        `tracks()`.  -> (spawned [B] i32, dropped [1] i32: candidates that found no
+        room), per-batch-size buffers.  No synchronisation: `n` becomes an upper
+        bound until `size()`."""
+        B = int(poses.shape[0])
+        if self.owner is None or int(self.owner.shape[0]) != B:
+            raise ValueError("LandmarkMap.spawn: no observe call of this batch size")
+        if rows is None:
+            if not self._tracks:
+                raise ValueError("LandmarkMap.spawn: no kept observe rows; pass rows and rows_count")
+            rows, rows_count = self._tracks[-1]
+        p_cap = int(Xc.shape[1])
+        if tuple(Xc.shape) != (B, p_cap, 3) or tuple(pairs.shape) != (B, p_cap, 2) or \
+                tuple(kp.shape) != (B, self.kp_cap, 5) or tuple(desc.shape) != (B, self.kp_cap, 32):
+            raise ValueError("LandmarkMap.spawn: Xc / pairs / kp / desc do not match (B, p_cap, kp_cap)")
+        if int(rows.shape[0]) != B:
+            raise ValueError("LandmarkMap.spawn: rows of another batch size")
+        b = self._life_buffers(B)
+        keyframe = to_dev(keyframe, torch.uint8)
+        _lib.call("slam_map_spawn", ptr(Xc), ptr(pairs), ptr(count), p_cap, ptr(kp), ptr(desc),
+                  ptr(n_kp), self.kp_cap, ptr(self.owner), ptr(poses), ptr(keyframe), B,
+                  float(z_range[0]), float(z_range[1]), int(frame0), ptr(self.X), ptr(self.desc),
+                  ptr(self.visible), ptr(self.found), ptr(self.born), ptr(self.last),
+                  ptr(self.n_dev), self.cap, ptr(rows), ptr(rows_count), int(rows.shape[1]),
+                  ptr(b["spawned"]), ptr(b["dropped"]), ptr(b["ws"]), b["ws"].numel(),
+                  stream_ptr(stream))
+        self.n, self._exact = self.cap, False   # a bound that also holds for a graph's replays
+        self.spawned, self.dropped = b["spawned"], b["dropped"]
+        return self.spawned, self.dropped
+
+    def cull(self, now, min_visible=4, ratio=(1, 4), age=4, min_found=2, stream=None):
+        """Drop the landmarks that do not hold up (slam_map_cull): found in fewer
+        than ratio of at least min_visible predicted views, or found fewer than
+        min_found times `age` frames after birth.  Their position becomes NaN;
+        their index stays.  -> nculled [1] i32 (device)."""
+        if self.nculled is None:
+            self.nculled = torch.zeros((1,), dtype=torch.int32, device=self.dev)
+        _lib.call("slam_map_cull", ptr(self.X), ptr(self.visible), ptr(self.found), ptr(self.born),
+                  ptr(self.n_dev), self.cap, int(now), int(min_visible), int(ratio[0]),
+                  int(ratio[1]), int(age), int(min_found), ptr(self.nculled), stream_ptr(stream))
+        return self.nculled
+
+    def compact(self, stream=None):
+        """Squeeze the dead landmarks out (slam_map_compact; the order of the
+        others is kept), renumber the kept track tensors (slam_rows_remap) and read
+        the new count: synchronises.  -> remap [capacity] i32, the new index of
+        every old one or -1.  What the last observe left (uv, owner, ...) still
+        speaks of the old indices: score and spawn before compacting."""
+        if self._alt is None:
+            self._alt = tuple(torch.zeros_like(t) for t in self._fields())
+            self.remap = torch.full((self.cap,), -1, dtype=torch.int32, device=self.dev)
+        with torch.cuda.stream(stream):
+            n_out = torch.zeros_like(self.n_dev)
+            _lib.call("slam_map_compact", *(ptr(t) for t in self._fields()), ptr(self.n_dev),
+                      self.cap, *(ptr(t) for t in self._alt), ptr(self.remap), ptr(n_out),
+                      stream_ptr(stream))
+            self.n_dev.copy_(n_out)   # in place: a captured graph keeps reading this tensor
+            old = self._fields()
+            self.X, self.desc, self.visible, self.found, self.born, self.last = self._alt
+            self._alt = old
+            kept = []
+            for rows, count in self._tracks:
+                out = (torch.zeros_like(rows), torch.zeros_like(count))
+                _lib.call("slam_rows_remap", ptr(rows), ptr(count), int(rows.shape[1]),
+                          int(rows.shape[0]), ptr(self.remap), self.cap, ptr(out[0]), ptr(out[1]),
+                          stream_ptr(stream))
+                kept.append(out)
+            self._tracks = kept
+            self.n, self._exact = int(self.n_dev.item()), True
+        return self.remap
+
+    def step(self, frame0, poses, kp, desc, n_kp, Xc, pairs, count, keyframe, z_range=(0.1, 70.0),
+             cull=None, stream=None, **localize_options):
+        """One batch of frames through the map: `localize` from the predicted
+        poses, `score` its second pass, `spawn` at the refined poses from the
+        frames with keyframe != 0 and status 0, `cull` at now = frame0 + B - 1
+        (`cull`: a dict of its options).  -> what `localize` returns.  One stream,
+        no host synchronisation: after a first call has allocated the buffers it
+        can be captured in a graph."""
+        B = int(poses.shape[0])
+        with torch.cuda.stream(stream):
+            res = self.localize(frame0, poses, kp, desc, n_kp, stream=stream, **localize_options)
+            self.score(frame0, stream=stream)
+            flags = (to_dev(keyframe, torch.uint8).ne(0) & res[5].eq(0)).to(torch.uint8)
+            self.spawn(frame0, res[0], Xc, pairs, count, kp, desc, n_kp, flags, z_range=z_range,
+                       stream=stream)
+            self.cull(frame0 + B - 1, stream=stream, **(cull or {}))
+        return res
+
+    def tracks(self, compact=False, drop_dead=True):
         """Synchronises: the rows of every observe call so far, concatenated
         ([n,4] f64: frame, landmark, x, y) -- problem_from_map's optimization
-        matrix.  With compact=True the landmarks that were never observed are
+        matrix.  With drop_dead the rows of landmarks that `cull` dropped are left
+        out.  With compact=True the landmarks that were never observed are
         left out: returns (rows with the landmark column renumbered, ids) where
         ids [k] are the map indices, so X[ids] are the problem's points."""
         out = [np.zeros((0, 4))]
@@ -251,6 +408,11 @@ class LandmarkMap:
             r, c = rows.cpu().numpy(), count.cpu().numpy()
             out += [r[i, :c[i]] for i in range(len(c))]
         om = np.concatenate(out, 0)
+        if drop_dead and len(om):
+            dead = np.isnan(self.X[:, 0].cpu().numpy())
+            l = om[:, 1].astype(np.int64)
+            inside = (l >= 0) & (l < self.cap)
+            om = om[~(inside & dead[np.where(inside, l, 0)])]
         if not compact:
             return om
         ids, inv = np.unique(om[:, 1].astype(np.int64), return_inverse=True)
