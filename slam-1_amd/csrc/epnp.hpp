@@ -23,13 +23,19 @@ constexpr int kEpnpWs = 4 * EPNP_MAXN + 48 + 60;
 /* cyclic Jacobi on the symmetric n x n matrix A (row-major, destroyed: its
  * diagonal ends as the eigenvalues); V (row-major) gets the eigenvectors as
  * columns.  Fixed rule: sweeps until the off-diagonal mass is below 1e-30 of
- * the diagonal mass, at most 40. */
-template <int n>
+ * the diagonal mass, at most 40.
+ * kWaveExit: the lanes that call it together leave the sweep loop together
+ * (a lane that has met the rule idles through the others' sweeps), the same
+ * operations per lane.  With each lane leaving on its own, the compiler keeps
+ * A and V a second time for the lanes that have left (36 more registers at
+ * n = 3) -- what set the eigen kernel's register count. */
+template <int n, bool kWaveExit = false>
 __device__ __forceinline__ void ep_jacobi(double* A, double* V) {
   #pragma unroll
   for (int i = 0; i < n; ++i)
     #pragma unroll
     for (int j = 0; j < n; ++j) V[i * n + j] = i == j ? 1.0 : 0.0;
+  bool done = false;
   #pragma unroll 1
   for (int sweep = 0; sweep < 40; ++sweep) {
     double off = 0.0, dia = 0.0;
@@ -39,7 +45,13 @@ __device__ __forceinline__ void ep_jacobi(double* A, double* V) {
       #pragma unroll
       for (int j = i + 1; j < n; ++j) off += A[i * n + j] * A[i * n + j];
     }
-    if (!(off > 1e-30 * dia)) break;
+    if (kWaveExit) {
+      done = done || !(off > 1e-30 * dia);
+      if (__ballot(!done) == 0ull) break;
+      if (done) continue;
+    } else if (!(off > 1e-30 * dia)) {
+      break;
+    }
     constexpr int kUnroll = n <= 4 ? 4 : 1;
     #pragma unroll kUnroll
     for (int p = 0; p < n - 1; ++p)
@@ -289,31 +301,49 @@ __device__ inline void ep_rvec(const double R[9], double r[3]) {
 
 // ---------------------------------------------------------------- group form
 // One EPnP in two kernels (csrc/geometry.hip), each of one-wave workgroups.
-// Eigen kernel, a 16-lane group per hypothesis (lane k = lane & 15 of group
-// g = lane >> 4): the steps that dominate -- M^T M and its 12x12 Jacobi
-// eigen-decomposition -- run with lanes k < 12 owning row k, the sample, the
-// control points and the eigen ordering on lane 0.  Beta kernel, a 4-lane
-// group per hypothesis: L and rho on lane 0, the three beta approximations on
-// lanes 0..2, the choice on lane 0; it holds the registers of that long serial
-// chain on a quarter of the waves.  Every value is computed with the
-// operations of oracle/epnp.h in the same order.  A workgroup is one wave, so
-// __syncthreads() is a cheap wave-level fence.
-constexpr int kJld = 13;  // row stride of the Jacobi buffers (odd: rows on distinct banks)
+// Eigen kernel, a 12-lane group per hypothesis (group g = lane / 12, lane
+// k = lane % 12 of it; lanes 60..63 of the wave idle): the steps that dominate
+// -- M^T M and its 12x12 Jacobi eigen-decomposition -- run with lane k owning
+// row k, the sample, the control points and the eigen ordering on lane 0.
+// Beta kernel, a 4-lane group per hypothesis: L and rho on lane 0, the three
+// beta approximations on lanes 0..2, the choice on lane 0; it holds the
+// registers of that long serial chain on a quarter of the waves.  Every value
+// is computed with the operations of oracle/epnp.h in the same order.  A
+// workgroup is one wave, so __syncthreads() is a cheap wave-level fence.
+constexpr int kEigLanes = 12;               // lanes of a hypothesis = rows of M^T M
+constexpr int kEigGroups = 64 / kEigLanes;  // hypotheses a wave
 struct EpGroup {         // LDS of one group of the eigen kernel
-  double A[144], V[144]; // M^T M (destroyed: eigenvalues on the diagonal), eigenvectors
   double alph[4 * EPNP_MAXN];
   double cw[4][3];
   double offdia[2];
-  double B[2][12 * kJld];  // Jacobi: A ping-pong (round r reads B[cur], writes B[cur ^ 1])
   double cs[12];           // Jacobi: the round's (c, s) of the 6 pairs
   double part[24];         // Jacobi: per-row diagonal / off-diagonal squares
-  double pad[3];
+  double pad[23];
   int o12[4];            // columns of V of the 4 smallest eigenvalues, ascending
   int flag;              // 0: degenerate, 1: ok; Jacobi: 1 while sweeping
 };
-// consecutive groups 32 banks apart, so lanes 0..15 and 16..31 of a wave
-// (one ds_read_b64 bank group) never collide on the stride-13 rows
-static_assert(sizeof(EpGroup) % 256 == 128, "EpGroup stride must be 128 mod 256 bytes");
+// A 32-lane half of the wave (one ds_read_b64 pass; a double sits on bank pair
+// index mod 32) holds two whole groups and part of a third.  Consecutive
+// groups 12 doubles (mod 32) apart: what the lanes of a group read at one
+// address (cs, flag, alph: a broadcast) lands on bank pairs 0, 12, 24 (lanes
+// 0..31) and 24, 4, 16 (lanes 32..63), and what they index by k (part) is
+// contiguous over the lanes of the wave.
+static_assert(sizeof(EpGroup) % 256 == 96, "EpGroup stride must be 12 mod 32 doubles");
+// M^T M of the whole wave (destroyed by the Jacobi: eigenvalues on the
+// diagonal; the only copy, the Jacobi works in place), column-major with the
+// groups side by side: element (row, col) of group g at B[col * kJl + 12 * g +
+// row].  A lane reads and writes its own row one column at a time, so an access
+// of the wave touches consecutive doubles -- distinct bank pairs in either
+// 32-lane half of a read and in every 16-lane quarter of a ds_write_b64.  A
+// partner row is a permutation inside the group: also distinct for the two
+// whole groups of a half; the group that straddles the halves can meet at most
+// its own 4 slots of the other half (2-way), the least three groups of 12 rows
+// can have on 32 bank pairs.  The eigenvectors never reach LDS: lane k keeps
+// row k of V in registers and writes its entries of the record from there.
+constexpr int kJl = 12 * kEigGroups;
+struct EpJacobi {
+  double B[12 * kJl];
+};
 
 // What the eigen kernel hands to the beta kernel, per hypothesis, through
 // global memory (kEpRec doubles: flag .. v), and the beta kernel's LDS of one
@@ -345,7 +375,7 @@ __device__ __forceinline__ int ep_bary(const double* pw, EpGroup& G) {
   for (int i = 0; i < n; ++i)
     for (int a = 0; a < 3; ++a)
       for (int b = 0; b < 3; ++b) A3[3 * a + b] += (pw[3 * i + a] - cw[0][a]) * (pw[3 * i + b] - cw[0][b]);
-  ep_jacobi<3>(A3, V3);
+  ep_jacobi<3, true>(A3, V3);
   int ord[3] = {0, 1, 2};
   for (int i = 0; i < 3; ++i)
     for (int j = i + 1; j < 3; ++j)
@@ -389,7 +419,7 @@ __device__ __forceinline__ int ep_bary(const double* pw, EpGroup& G) {
 // row r of M^T M: sum over points i (in order) of m1[r] m1[c] + m2[r] m2[c]
 template <int n>
 __device__ __forceinline__ void ep_mtm_row(int r, const double* uv, double fx, double fy, double cx,
-                                           double cy, EpGroup& G) {
+                                           double cy, const EpGroup& G, double* J) {
   double acc[12];
 #pragma unroll
   for (int c = 0; c < 12; ++c) acc[c] = 0.0;
@@ -409,19 +439,19 @@ __device__ __forceinline__ void ep_mtm_row(int r, const double* uv, double fx, d
     for (int c = 0; c < 12; ++c) acc[c] += m1r * m1[c] + m2r * m2[c];
   }
 #pragma unroll
-  for (int c = 0; c < 12; ++c) G.A[12 * r + c] = acc[c];
+  for (int c = 0; c < 12; ++c) J[c * kJl + r] = acc[c];
 }
 
 // The 12x12 Jacobi of M^T M with the round-robin ordering of
-// oracle/epnp.h ep_jacobi12_par: lanes k < 12 of the group own row k of A
-// (in LDS, ping-pong B[cur] -> B[cur ^ 1]) and of V (in registers).  Per
-// round: lanes 0..5 derive pair k's (c, s) from the round-start matrix and
-// publish them; then every lane rotates the column pairs of its own row AND
-// of its partner's row (A J, the same operations the partner performs), and
-// forms its new row from the two (J^T (A J)) -- one exchange through LDS
-// per round, rounds fully unrolled so the pair columns are compile-time
-// register indices.  The wave loops until every group has met its own
-// stopping rule; a finished group keeps copying its rows.
+// oracle/epnp.h ep_jacobi12_par: lane k of the group owns row k of A (in LDS,
+// EpJacobi) and of V (in registers).  Per round: lanes 0..5 derive pair k's
+// (c, s) from the round-start matrix and publish them; then every lane rotates
+// the column pairs of its own row AND of its partner's row (A J, the same
+// operations the partner performs), and forms its new row from the two
+// (J^T (A J)) -- one exchange through LDS per round, rounds fully unrolled so
+// the pair columns are compile-time register indices.  The wave loops until
+// every group has met its own stopping rule; a finished group keeps copying
+// its rows.
 __device__ __forceinline__ void ep_pairs12(int r, int pp[6], int qq[6]) {
   int a[12];
   a[0] = 0;
@@ -446,12 +476,25 @@ __device__ __forceinline__ void ep_rot_cs(double app, double aqq, double apq, do
   s = z ? 0.0 : t * cc;
 }
 
+// One round, in place.  J: the wave's EpJacobi::B at the group's first slot.
+// The six disjoint column pairs stream through: a pair's four entries (the
+// lane's own row and its partner's, columns P and Q) are rotated (A J), combined
+// with the (c, s) of the pair holding row kr (J^T (A J)) and stored over the
+// lane's own entries, while the entries of the pairs kJacAhead further on are
+// on their way from LDS; the first kJacAhead pairs are read before the barrier,
+// under the (c, s) chain of lanes 0..5.  Only V's row and kJacAhead + 1 pairs'
+// operands are in registers at any time.
+// In place is safe because the workgroup is one wave, whose LDS instructions
+// complete in program order: the partner's read of this lane's entries of a pair
+// is the same instruction as this lane's own read of them, issued before the
+// instruction that stores the pair, and no later pair touches its columns.
+// One pair ahead measured shortest (profiles/pnp_eig_groups/: the Jacobi of a
+// wave +1.5 % at 2, +2 % at 3, +10 % with all six read before the barrier).
+constexpr int kJacAhead = 1;
 template <int r>
-__device__ __forceinline__ void ep_jacobi_round(EpGroup& G, int k, int kr, bool act, int cur,
+__device__ __forceinline__ void ep_jacobi_round(EpGroup& G, double* J, int k, int kr, bool act,
                                                 double (&vr)[12]) {
-  constexpr int n = 12, ld = kJld;
-  const double* A0 = G.B[cur];
-  double* A1 = G.B[cur ^ 1];
+  constexpr int n = 12, ld = kJl;
   int pp[6], qq[6];
   ep_pairs12(r, pp, qq);
   if (k < 6) {
@@ -459,7 +502,7 @@ __device__ __forceinline__ void ep_jacobi_round(EpGroup& G, int k, int kr, bool 
     const int x = k == 0 ? 0 : 1 + (k - 1 + r) % 11, y = 1 + (10 - k + r) % 11;
     const int p = x < y ? x : y, q = x < y ? y : x;
     double c, s;
-    ep_rot_cs(A0[p * ld + p], A0[q * ld + q], A0[p * ld + q], c, s);
+    ep_rot_cs(J[p * ld + p], J[q * ld + q], J[q * ld + p], c, s);
     G.cs[2 * k] = c;
     G.cs[2 * k + 1] = s;
   }
@@ -470,83 +513,66 @@ __device__ __forceinline__ void ep_jacobi_round(EpGroup& G, int k, int kr, bool 
   const int partner = ppos == 0 ? 0 : 1 + (ppos - 1 + r) % 11;
   const int pi = pos < ppos ? pos : ppos;
   const bool isp = kr < partner;
-  double row[n], prow[n];
+  double akp[6], akq[6], bkp[6], bkq[6];  // pair i: own row, partner's row
 #pragma unroll
-  for (int j = 0; j < n; ++j) {
-    row[j] = A0[kr * ld + j];
-    prow[j] = A0[partner * ld + j];
+  for (int i = 0; i < kJacAhead; ++i) {
+    akp[i] = J[pp[i] * ld + kr];
+    akq[i] = J[qq[i] * ld + kr];
+    bkp[i] = J[pp[i] * ld + partner];
+    bkq[i] = J[qq[i] * ld + partner];
   }
   __syncthreads();
-  double c[6], s[6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    c[i] = G.cs[2 * i];
-    s[i] = G.cs[2 * i + 1];
-  }
-  double ck = c[0], sk = s[0];
-#pragma unroll
-  for (int i = 1; i < 6; ++i) {
-    ck = pi == i ? c[i] : ck;
-    sk = pi == i ? s[i] : sk;
-  }
-  double out[n];
-#pragma unroll
-  for (int j = 0; j < n; ++j) out[j] = row[j];
-  // columns (A J, V J): the pairs are disjoint, any order
+  const double ck = G.cs[2 * pi], sk = G.cs[2 * pi + 1];
 #pragma unroll
   for (int i = 0; i < 6; ++i) {
     const int P = pp[i], Q = qq[i];
-    const double akp = row[P], akq = row[Q];
-    row[P] = c[i] * akp - s[i] * akq;
-    row[Q] = s[i] * akp + c[i] * akq;
-    const double bkp = prow[P], bkq = prow[Q];
-    prow[P] = c[i] * bkp - s[i] * bkq;
-    prow[Q] = s[i] * bkp + c[i] * bkq;
+    if (i + kJacAhead < 6) {
+      const int j = i + kJacAhead;
+      akp[j] = J[pp[j] * ld + kr];
+      akq[j] = J[qq[j] * ld + kr];
+      bkp[j] = J[pp[j] * ld + partner];
+      bkq[j] = J[qq[j] * ld + partner];
+    }
+    const double c = G.cs[2 * i], s = G.cs[2 * i + 1];
+    // columns (A J, V J): the pairs are disjoint, any order
+    const double rp = c * akp[i] - s * akq[i], rq = s * akp[i] + c * akq[i];
+    const double tp = c * bkp[i] - s * bkq[i], tq = s * bkp[i] + c * bkq[i];
     const double vkp = vr[P], vkq = vr[Q];
-    const double wp = c[i] * vkp - s[i] * vkq, wq = s[i] * vkp + c[i] * vkq;
+    const double wp = c * vkp - s * vkq, wq = s * vkp + c * vkq;
     vr[P] = act ? wp : vkp;
     vr[Q] = act ? wq : vkq;
-  }
-  // pin V's rotated values here: left free, the compiler defers the V chain
-  // and keeps every round's (c, s) live across the sweep (22 VGPRs a round)
-#pragma unroll
-  for (int j = 0; j < n; ++j) asm volatile("" : "+v"(vr[j]));
-  // rows (J^T (A J)) of the pair holding k; a finished group copies its row
-#pragma unroll
-  for (int j = 0; j < n; ++j) {
-    const double nv = isp ? ck * row[j] - sk * prow[j] : sk * prow[j] + ck * row[j];
-    out[j] = act ? nv : out[j];
-  }
-  if (k < n) {
-#pragma unroll
-    for (int j = 0; j < n; ++j) A1[k * ld + j] = out[j];
+    // pin V's rotated values here: left free, the compiler defers the V chain
+    // and keeps every round's (c, s) live across the sweep
+    asm volatile("" : "+v"(vr[P]), "+v"(vr[Q]));
+    // rows (J^T (A J)) of the pair holding k; a finished group copies its row
+    const double np = isp ? ck * rp - sk * tp : sk * tp + ck * rp;
+    const double nq = isp ? ck * rq - sk * tq : sk * tq + ck * rq;
+    if (k < n) {
+      J[P * ld + k] = act ? np : akp[i];
+      J[Q * ld + k] = act ? nq : akq[i];
+    }
   }
   __syncthreads();
 }
 
-__device__ __forceinline__ void ep_jacobi12_group(EpGroup& G, int k, bool live) {
-  constexpr int n = 12, ld = kJld;
+__device__ __forceinline__ void ep_jacobi12_group(EpGroup& G, double* J, int k, bool live,
+                                                  double (&vr)[12]) {
+  constexpr int n = 12, ld = kJl;
   const bool own = k < n;
   const int kr = own ? k : 0;
-  double vr[n];
 #pragma unroll
   for (int j = 0; j < n; ++j) vr[j] = kr == j ? 1.0 : 0.0;
-  if (own) {
-#pragma unroll
-    for (int j = 0; j < n; ++j) G.B[0][k * ld + j] = G.A[k * n + j];
-  }
   if (k == 0) G.flag = live ? 1 : 0;
   __syncthreads();
-  int cur = 0;
   for (int sweep = 0; sweep < 40; ++sweep) {
     // off / dia by rows: row k's squares, then lane 0 sums the rows in order
     if (own) {
-      const double* Ar = G.B[cur] + k * ld;
+      const double* Ar = J + k;
       double o = 0.0;
 #pragma unroll
       for (int j = 1; j < n; ++j)
-        if (j > k) o += Ar[j] * Ar[j];
-      G.part[k] = Ar[k] * Ar[k];
+        if (j > k) o += Ar[j * ld] * Ar[j * ld];
+      G.part[k] = Ar[k * ld] * Ar[k * ld];
       G.part[n + k] = o;
     }
     __syncthreads();
@@ -564,37 +590,33 @@ __device__ __forceinline__ void ep_jacobi12_group(EpGroup& G, int k, bool live) 
 #ifdef SLAM_PNPH_TRACE
     if (threadIdx.x == 0) G.offdia[1] = sweep + 1;
 #endif
-    ep_jacobi_round<0>(G, k, kr, act, cur, vr);
-    ep_jacobi_round<1>(G, k, kr, act, cur ^ 1, vr);
-    ep_jacobi_round<2>(G, k, kr, act, cur, vr);
-    ep_jacobi_round<3>(G, k, kr, act, cur ^ 1, vr);
-    ep_jacobi_round<4>(G, k, kr, act, cur, vr);
-    ep_jacobi_round<5>(G, k, kr, act, cur ^ 1, vr);
-    ep_jacobi_round<6>(G, k, kr, act, cur, vr);
-    ep_jacobi_round<7>(G, k, kr, act, cur ^ 1, vr);
-    ep_jacobi_round<8>(G, k, kr, act, cur, vr);
-    ep_jacobi_round<9>(G, k, kr, act, cur ^ 1, vr);
-    ep_jacobi_round<10>(G, k, kr, act, cur, vr);
-    cur ^= 1;  // 11 rounds: odd
+    // opaque lane indices: every round derives its partner, its pair and their
+    // LDS addresses where it uses them (hoisted out of the sweep loop, the 11
+    // rounds' worth of them would stay in registers for the whole Jacobi)
+    int ko = k, ro = kr;
+    asm volatile("" : "+v"(ko), "+v"(ro));
+    ep_jacobi_round<0>(G, J, ko, ro, act, vr);
+    ep_jacobi_round<1>(G, J, ko, ro, act, vr);
+    ep_jacobi_round<2>(G, J, ko, ro, act, vr);
+    ep_jacobi_round<3>(G, J, ko, ro, act, vr);
+    ep_jacobi_round<4>(G, J, ko, ro, act, vr);
+    ep_jacobi_round<5>(G, J, ko, ro, act, vr);
+    ep_jacobi_round<6>(G, J, ko, ro, act, vr);
+    ep_jacobi_round<7>(G, J, ko, ro, act, vr);
+    ep_jacobi_round<8>(G, J, ko, ro, act, vr);
+    ep_jacobi_round<9>(G, J, ko, ro, act, vr);
+    ep_jacobi_round<10>(G, J, ko, ro, act, vr);
   }
-  if (own) {
-#pragma unroll
-    for (int j = 0; j < n; ++j) {
-      G.A[k * n + j] = G.B[cur][k * ld + j];
-      G.V[k * n + j] = vr[j];
-    }
-  }
-  __syncthreads();
 }
 
 // eigen ordering (lane 0 of the eigen kernel): the columns of V of the 4
 // smallest eigenvalues -> G.o12
-__device__ __forceinline__ void ep_order(EpGroup& G) {
+__device__ __forceinline__ void ep_order(EpGroup& G, const double* J) {
   int o12[12];
   for (int i = 0; i < 12; ++i) o12[i] = i;
   for (int i = 0; i < 4; ++i)
     for (int j = i + 1; j < 12; ++j)
-      if (G.A[13 * o12[j]] < G.A[13 * o12[i]]) {
+      if (J[(kJl + 1) * o12[j]] < J[(kJl + 1) * o12[i]]) {
         const int tmp = o12[i]; o12[i] = o12[j]; o12[j] = tmp;
       }
   for (int k = 0; k < 4; ++k) G.o12[k] = o12[k];

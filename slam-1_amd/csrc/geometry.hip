@@ -218,15 +218,17 @@ __device__ void lm_group(const double* Q, const double* q, int n, const Cam& K, 
 // 5 points from that pose (a degenerate sample starts LM at r = t = 0).
 // Poses -> ws [b][h][6].  Three kernels of one-wave workgroups, each holding
 // only the registers of its own phase beside ORB's workgroups:
-//   k_pnp_hyp_eig   kHypGroups hypotheses a wave, 16 lanes each: sample,
-//                   control points, M^T M rows and the 12x12 Jacobi on 12
-//                   lanes, the 4 smallest eigenvectors -> a record of kEpRec
+//   k_pnp_hyp_eig   kEigGroups hypotheses a wave, 12 lanes each (4 lanes
+//                   idle): sample, control points, M^T M rows and the 12x12
+//                   Jacobi, the 4 smallest eigenvectors -> a record of kEpRec
 //                   doubles per hypothesis in the scratch buffer;
 //   k_pnp_hyp_beta  kBetaGroups hypotheses a wave, 4 lanes each: L and rho,
 //                   the three beta approximations on 3 lanes (the long serial
 //                   chain, a quarter of the waves), the choice -> ws;
 //   k_pnp_hyp_lm    kHypGroups hypotheses a wave, 16 lanes each: the sample LM.
-constexpr int kHypGroups = 4;    // k_pnp_hyp_eig: hypotheses per workgroup (16 lanes each)
+constexpr int kEigGroups = slam_epnp::kEigGroups;  // k_pnp_hyp_eig: hypotheses per workgroup
+constexpr int kEigLanes = slam_epnp::kEigLanes;    // ... on this many lanes each
+constexpr int kHypGroups = 4;    // k_pnp_hyp_lm: hypotheses per workgroup (16 lanes each)
 constexpr int kBetaGroups = 16;  // k_pnp_hyp_beta: hypotheses per workgroup (4 lanes each)
 constexpr int kEpRec = slam_epnp::kEpRec;
 #ifdef SLAM_PNPH_TRACE
@@ -272,15 +274,20 @@ __global__ __launch_bounds__(64) void k_pnp_hyp_eig(const double* __restrict__ Q
 #ifdef SLAM_PNP_PRIO
   __builtin_amdgcn_s_setprio(SLAM_PNP_PRIO);
 #endif
-  __shared__ slam_epnp::EpGroup grp[kHypGroups];
-  __shared__ double spw[kHypGroups][3 * kMinSample], suv[kHypGroups][2 * kMinSample];
-  __shared__ int sidx[kHypGroups][kMinSample];
+  __shared__ slam_epnp::EpGroup grp[kEigGroups];
+  __shared__ slam_epnp::EpJacobi jac;
+  __shared__ double spw[kEigGroups][3 * kMinSample], suv[kEigGroups][2 * kMinSample];
+  __shared__ int sidx[kEigGroups][kMinSample];
   const int b = blockIdx.x, t = threadIdx.x;
-  const int g = t >> 4, k = t & 15;
-  const int h = blockIdx.y * kHypGroups + g;
+  // lanes past the last group ride along on the last group's LDS as a lane
+  // that owns no row (k = kEigLanes): they read, reach every barrier, write nothing
+  const bool idle = t >= kEigGroups * kEigLanes;
+  const int g = idle ? kEigGroups - 1 : t / kEigLanes;
+  const int k = idle ? kEigLanes : t - g * kEigLanes;
+  const int h = blockIdx.y * kEigGroups + g;
   const int L = min(max(count[b], 0), cap);
   if (L < kMinSample) return;  // uniform over the workgroup
-  const bool live = h < n_hyp;
+  const bool live = !idle && h < n_hyp;
   const double* Q = Qall + (size_t)b * cap * 3;
   const double* q = qall + (size_t)b * cap * 2;
   const Cam K{Kp[0], Kp[4], Kp[2], Kp[5]};
@@ -293,27 +300,35 @@ __global__ __launch_bounds__(64) void k_pnp_hyp_eig(const double* __restrict__ Q
   __syncthreads();
   PNPH_T(1);
   bool ok = live && G.flag != 0;
-  if (ok && k < 12) slam_epnp::ep_mtm_row<kMinSample>(k, suv[g], K.fx, K.fy, K.cx, K.cy, G);
+  double* J = jac.B + 12 * g;
+  if (ok && k < 12) slam_epnp::ep_mtm_row<kMinSample>(k, suv[g], K.fx, K.fy, K.cx, K.cy, G, J);
   __syncthreads();
   PNPH_T(2);
-  slam_epnp::ep_jacobi12_group(G, k, ok);
+  double vr[12];  // row k of the eigenvectors
+  slam_epnp::ep_jacobi12_group(G, J, k, ok, vr);
   PNPH_T(3);
 #ifdef SLAM_PNPH_TRACE
   if (threadIdx.x == 0 && blockIdx.x == 3 && blockIdx.y == 5) g_pnph[7] = (unsigned long long)G.offdia[1];
 #endif
-  if (ok && k == 0) slam_epnp::ep_order(G);
+  if (ok && k == 0) slam_epnp::ep_order(G, J);
   __syncthreads();
   if (live) {
     double* rec = scr + ((size_t)b * n_hyp + h) * kEpRec;
     if (k == 0) rec[0] = ok ? 1.0 : 0.0;
     if (ok) {
-      if (k < 3 * kMinSample) rec[1 + k] = spw[g][k];
-      if (k < 2 * kMinSample) rec[16 + k] = suv[g][k];
-      for (int i = k; i < 4 * kMinSample; i += 16) rec[26 + i] = G.alph[i];
+      for (int i = k; i < 3 * kMinSample; i += kEigLanes) rec[1 + i] = spw[g][i];
+      for (int i = k; i < 2 * kMinSample; i += kEigLanes) rec[16 + i] = suv[g][i];
+      for (int i = k; i < 4 * kMinSample; i += kEigLanes) rec[26 + i] = G.alph[i];
       if (k < 12) {
         rec[46 + k] = G.cw[k / 3][k % 3];
         // row k of the 4 null vectors: v[kk][k] = V[k][o12[kk]]
-        for (int kk = 0; kk < 4; ++kk) rec[58 + 12 * kk + k] = G.V[12 * k + G.o12[kk]];
+        for (int kk = 0; kk < 4; ++kk) {
+          const int o = G.o12[kk];
+          double v = vr[0];
+#pragma unroll
+          for (int j = 1; j < 12; ++j) v = o == j ? vr[j] : v;
+          rec[58 + 12 * kk + k] = v;
+        }
       }
     }
   }
@@ -1112,13 +1127,14 @@ extern "C" int slam_pnp_ransac_ws(const double* d_Q, const double* d_q, const in
     return SLAM_ERR_WORKSPACE;
   }
   hipStream_t s = slam::as_stream(stream);
-  const dim3 egrid(batch, (n_hyp + kHypGroups - 1) / kHypGroups);
+  const dim3 egrid(batch, (n_hyp + kEigGroups - 1) / kEigGroups);
   k_pnp_hyp_eig<<<egrid, 64, 0, s>>>(d_Q, d_q, d_count, cap, d_K, seed, item0, n_hyp, d_scratch);
   SLAM_LAUNCHED("k_pnp_hyp_eig");
   const dim3 bgrid(batch, (n_hyp + kBetaGroups - 1) / kBetaGroups);
   k_pnp_hyp_beta<<<bgrid, 64, 0, s>>>(d_count, cap, d_K, n_hyp, d_scratch, d_ws);
   SLAM_LAUNCHED("k_pnp_hyp_beta");
-  k_pnp_hyp_lm<<<egrid, 64, 0, s>>>(d_Q, d_q, d_count, cap, d_K, seed, item0, n_hyp, hyp_iters,
+  const dim3 lgrid(batch, (n_hyp + kHypGroups - 1) / kHypGroups);
+  k_pnp_hyp_lm<<<lgrid, 64, 0, s>>>(d_Q, d_q, d_count, cap, d_K, seed, item0, n_hyp, hyp_iters,
                                     d_ws);
   SLAM_LAUNCHED("k_pnp_hyp_lm");
   k_pnp<<<batch, kPnPWG, 0, s>>>(d_Q, d_q, d_count, cap, d_K, seed, item0, n_hyp, reproj_thresh,
