@@ -541,6 +541,92 @@ int slam_rows_remap(const double* d_rows, const int32_t* d_count, int rows_cap, 
                     void* stream);
 
 /* ------------------------------------------------------------------------
+ * Relocalization: the pose of a frame in the map WITHOUT a predicted pose --
+ * what lost tracking and loop closure need.  The frame's keypoints are matched
+ * against the descriptors of all eligible landmarks (no window), every landmark
+ * keeps at most one keypoint (slam_match_unique with the roles swapped: queries
+ * are keypoints, targets are landmarks, so d_owner [batch][x_cap] names the
+ * keypoint a landmark won), the matches become track rows and PnP inputs,
+ * slam_pnp_ransac_ws finds a pose among them, and slam_pose_refine refines it
+ * and gives its information.  The three steps below are the new ones; each is
+ * asynchronous on `stream`, allocates nothing and never synchronises, and
+ * SLAM_ERR_ARG (a null pointer is reported by the argument's name) comes before
+ * any GPU call.  The map is the landmark state of the life cycle above: d_X,
+ * d_desc, d_last and the DEVICE count *d_n; it is only read.
+ *
+ * 1. Hamming kNN-2 against the live map.  Queries d_q [batch][q_cap][32] u8,
+ *    d_nq [batch] i32 (a negative count is 0, otherwise clamped to q_cap); the
+ *    map is shared by all items; d_range [batch][2] i32 = (lo_b, hi_b).
+ *    Landmark i is ELIGIBLE for item b iff
+ *      i < clamp(*d_n, 0, x_cap), d_X[i][0] is not NaN (alive) and
+ *      lo_b <= d_last[i] < hi_b.
+ *    For query j < nq_b the two smallest (distance, landmark index) pairs over
+ *    the eligible landmarks are reported, ties to the lower index:
+ *      d_idx2, d_dist2 [batch][q_cap][2] i32: full 32-bit landmark indices,
+ *             -1 / -1 where there is none
+ *      d_good [batch][q_cap] u8 = 1 iff both exist, d1 <= max_dist and
+ *             ratio_den d1 < ratio_num d2.
+ *    Two candidates are required, as in slam_hamming_knn2: this is a global
+ *    search, not a window.  Rows >= nq_b are not written.  An ineligible
+ *    landmark never appears in an output and never affects a ratio; the result
+ *    does not depend on the processing order.  d_range and *d_n are read on the
+ *    device: a captured graph can be replayed with other ranges and a grown map.
+ *    Two launches.  The map is cut into segments of SLAM_MAP_KNN_SEGMENT
+ *    landmarks and the grid is (query tile, segment, item), so one frame against
+ *    a large map fills the chip; a workgroup writes its queries' top-2 of its
+ *    segment to d_ws as dist << 20 | landmark, and the second launch merges the
+ *    segments per query and applies the ratio test.
+ *    d_ws: slam_hamming_map_workspace_bytes(batch, q_cap, x_cap) bytes (8 per
+ *    item, segment and query), 8-byte aligned, contents irrelevant on entry; a
+ *    smaller ws_bytes is an argument error that names the needed size.
+ *    1 <= x_cap <= 1 << 20, 1 <= q_cap <= 65535, 1 <= batch <= 65535, max_dist
+ *    in 0..256, 0 < ratio_num <= ratio_den <= 1 << 20; d_q and d_desc 16-byte
+ *    aligned. */
+#define SLAM_MAP_KNN_SEGMENT 2048
+int slam_hamming_map_segment(void); /* SLAM_MAP_KNN_SEGMENT of the built library */
+int slam_hamming_map_workspace_bytes(int batch, int q_cap, int x_cap, size_t* bytes);
+int slam_hamming_map_knn2(const uint8_t* d_q, const int32_t* d_nq, int q_cap,
+                          const uint8_t* d_desc, const double* d_X, const int32_t* d_last,
+                          const int32_t* d_n, int x_cap, const int32_t* d_range, int batch,
+                          int max_dist, int ratio_num, int ratio_den, int32_t* d_idx2,
+                          int32_t* d_dist2, uint8_t* d_good, void* d_ws, size_t ws_bytes,
+                          void* stream);
+
+/* 2. Rows and PnP inputs from the owners.  d_owner [batch][x_cap] i32 as
+ *    slam_match_unique wrote it with keypoints as queries and landmarks as
+ *    targets; d_kp [batch][kp_cap][5] f32.  For every landmark i < clamp(*d_n,
+ *    0, x_cap) with 0 <= j = owner[b][i] < kp_cap, in ascending i, row k gets
+ *      d_rows[b][k] = [frame0 + b, i, (double)kx_j, (double)ky_j]
+ *      d_Q[b][k]    = d_X[i]                  ([batch][rows_cap][3] f64)
+ *      d_q[b][k]    = ((double)kx_j, (double)ky_j)   ([batch][rows_cap][2] f64)
+ *    and d_count [batch] i32 counts them: the row format of slam_track_rows (so
+ *    slam_pose_refine takes d_rows unchanged) and the inputs of slam_pnp_ransac
+ *    with cap = rows_cap.  rows_cap >= min(x_cap, kp_cap) or an argument error.
+ *    One workgroup per frame.  1 <= batch <= 65535, 1 <= x_cap <= 1 << 20,
+ *    1 <= kp_cap <= 1 << 20. */
+int slam_reloc_rows(const int32_t* d_owner, const int32_t* d_n, int x_cap, const float* d_kp,
+                    int kp_cap, const double* d_X, int batch, int frame0, int rows_cap,
+                    double* d_rows, int32_t* d_count, double* d_Q, double* d_q, void* stream);
+
+/* 3. PnP result -> start pose of the refinement.  d_rvec, d_tvec [batch][3] f64
+ *    and d_ninl [batch] i32 as slam_pnp_ransac wrote them with K = d_P[:, :3]
+ *    (d_P [12] f64, 3x4, its left 3x3 upper triangular with a non-zero
+ *    diagonal: not checked here); d_count [batch] i32 the rows of step 2;
+ *    d_prior [batch][16] f64 camera-to-world poses, or NULL for the identity.
+ *    With s = K^-1 P[:, 3] by back substitution
+ *      s2 = P23 / P22, s1 = (P13 - P12 s2) / P11, s0 = ((P03 - P01 s1) - P02 s2) / P00
+ *    a frame with ninl >= min_inliers gets the camera-to-world pose
+ *      R' = Rod(rvec)^T, t' = -R' (tvec - s), last row 0 0 0 1,
+ *    and d_count_out[b] = d_count[b].  A frame with ninl < min_inliers (-1
+ *    included) gets its prior bit for bit and d_count_out[b] = 0:
+ *    slam_pose_refine then reports status 1 and returns that pose bit for bit,
+ *    so no second status word is needed.  d_poses [batch][16] f64 may not alias
+ *    d_prior.  1 <= batch <= 65535, min_inliers >= 0. */
+int slam_reloc_pose(const double* d_rvec, const double* d_tvec, const int32_t* d_ninl,
+                    const int32_t* d_count, const double* d_P, const double* d_prior, int batch,
+                    int min_inliers, double* d_poses, int32_t* d_count_out, void* stream);
+
+/* ------------------------------------------------------------------------
  * Tiled ORB detector + rBRIEF descriptor.
  *
  * Replaces orb_detector_using_tiles (/root/reference/orb.py:4-25), i.e. the

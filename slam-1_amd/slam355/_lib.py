@@ -128,6 +128,13 @@ SIGNATURES = {
                       c_p],
     "slam_map_compact": [c_p] * 7 + [c_int] + [c_p] * 9,
     "slam_rows_remap": [c_p, c_p, c_int, c_int, c_p, c_int, c_p, c_p, c_p],
+    "slam_hamming_map_segment": [],
+    "slam_hamming_map_workspace_bytes": [c_int, c_int, c_int, ctypes.POINTER(c_size_t)],
+    "slam_hamming_map_knn2": [c_p, c_p, c_int, c_p, c_p, c_p, c_p, c_int, c_p, c_int, c_int, c_int,
+                              c_int, c_p, c_p, c_p, c_p, c_size_t, c_p],
+    "slam_reloc_rows": [c_p, c_p, c_int, c_p, c_int, c_p, c_int, c_int, c_int, c_p, c_p, c_p, c_p,
+                        c_p],
+    "slam_reloc_pose": [c_p, c_p, c_p, c_p, c_p, c_p, c_int, c_int, c_p, c_p, c_p],
     "slam_fundamental_lmeds": [c_p, c_p, c_p, c_int, c_int, c_uint64, c_int, c_int, c_p, c_p, c_p,
                                c_p],
     "slam_fundamental_lmeds_ws": [c_p, c_p, c_p, c_int, c_int, c_uint64, c_int, c_int, c_p, c_p,

@@ -17,6 +17,9 @@ on a narrower search at the refined pose.  `score`, `spawn`, `cull` and
 `compact` let the map follow the camera (slam_map_score ... slam_map_compact):
 the landmark count lives on the device, so `step` -- localize, score, spawn
 from the keyframes, cull -- runs a batch of frames without a synchronisation.
+`LandmarkMap.relocalize` needs no predicted pose: a global Hamming search
+against the live landmarks (slam_hamming_map_knn2), PnP-RANSAC and the same
+refinement -- for lost tracking and for the measurement of a loop edge.
 """
 from __future__ import annotations
 
@@ -126,6 +129,9 @@ class LandmarkMap:
         self.rows_cap = max(min(self.cap, self.kp_cap), 1)   # track rows of one frame
         self._bufs = {}      # batch size -> the device buffers of observe
         self._rbufs = {}     # batch size -> the device buffers of localize
+        self._reloc = {}     # batch size -> the device buffers of relocalize
+        self._P_host = np.ascontiguousarray(P, np.float64).reshape(3, 4).copy()
+        self.pnp = self.start = self.matched = None   # relocalize: PnP's outputs, start poses, row counts
         self._tracks = []    # (rows, count) of every observe call
         self.uv = self.z = self.idx2 = self.dist2 = self.good = self.owner = None
         self.first = self.cost = None
@@ -267,6 +273,126 @@ class LandmarkMap:
                 rows, count, self.X, self.n, first[0], self.P, min_depth=min_depth,
                 out=b["second"], **refine_options)
         self.first, self.cost = first, cost
+        return po, rows, count, mask, ninl, status, info
+
+    def _reloc_buffers(self, B, n_hyp):
+        b = self._reloc.get(B)
+        if b is None:
+            f64 = dict(dtype=torch.float64, device=self.dev)
+            i32 = dict(dtype=torch.int32, device=self.dev)
+            u8 = dict(dtype=torch.uint8, device=self.dev)
+            b = dict(
+                range=torch.zeros((B, 2), **i32),
+                ws=matcher.map_knn2_workspace(B, self.kp_cap, self.cap, self.dev),
+                idx2=torch.full((B, self.kp_cap, 2), -1, **i32),
+                dist2=torch.full((B, self.kp_cap, 2), -1, **i32),
+                good0=torch.zeros((B, self.kp_cap), **u8), good=torch.zeros((B, self.kp_cap), **u8),
+                owner=torch.full((B, self.cap), -1, **i32),
+                Q=torch.zeros((B, self.rows_cap, 3), **f64), q=torch.zeros((B, self.rows_cap, 2), **f64),
+                pnp=(torch.zeros((B, 3), **f64), torch.zeros((B, 3), **f64), torch.zeros((B,), **i32),
+                     torch.zeros((B, self.rows_cap), **u8)),
+                K=self.P[:, :3].contiguous(), n_hyp=0,
+                start=torch.zeros((B, 4, 4), **f64), matched=torch.zeros((B,), **i32),
+                refine=(torch.zeros((B, 4, 4), **f64), torch.zeros((B, self.rows_cap), **u8),
+                        torch.zeros((B,), **i32), torch.zeros((B,), **i32),
+                        torch.zeros((B, 6, 6), **f64), torch.zeros((B,), **f64)),
+            )
+            self._reloc[B] = b
+        if b["n_hyp"] < n_hyp:   # the PnP workspace and scratch, held per batch size
+            b["pnp_ws"] = geometry.pnp_workspace(B, n_hyp, self.dev)
+            b["pnp_scratch"] = geometry.pnp_scratch(B, n_hyp, self.dev)
+            b["n_hyp"] = n_hyp
+        return b
+
+    def relocalize(self, frame0, kp, desc, n_kp, last_range=None, prior=None, max_dist=64,
+                   ratio=(7, 10), seed=0, item0=0, min_inliers=10, pnp=None, keep_tracks=False,
+                   stream=None, **refine_options):
+        """The poses of a batch of frames in the map without predicted poses: for
+        lost tracking and loop closure.  Every keypoint is matched against all
+        eligible landmarks (slam_hamming_map_knn2: alive, and `last` inside
+        `last_range`), every landmark keeps at most one keypoint
+        (slam_match_unique, keypoints as queries), the matches become track rows
+        and PnP inputs (slam_reloc_rows), PnP-RANSAC finds a pose among them
+        (slam_pnp_ransac_ws with K = P[:, :3], seed, item0 and `pnp` over
+        geometry.PNP_DEFAULTS), slam_reloc_pose turns it into the start pose and
+        geometry.refine_pose (its options in `refine_options`) refines it.
+
+        kp [B,kp_cap,5] f32, desc [B,kp_cap,32] u8, n_kp [B] i32.  last_range:
+        None (every landmark; INT32_MAX itself excluded), one (lo, hi) for all
+        frames, or an int32 [B,2] array or tensor; a device tensor is used as it
+        is, so a captured graph reads its current contents.  prior [B,4,4] f64
+        camera-to-world (None: the identity): what a frame whose PnP finds fewer
+        than min_inliers inliers comes back with, bit for bit, at status 1.
+
+        -> (poses [B,4,4] f64, rows, count, mask [B,rows_cap] u8, ninl [B] i32,
+        status [B] i32, info [B,6,6] f64) as `localize` returns them; count is 0
+        for a frame whose PnP failed.  rows and count are fresh tensors, the
+        others per-batch-size buffers overwritten by the next call of the same
+        batch size, as are `matched` (the rows written per frame, PnP's count),
+        `pnp` (rvec, tvec, ninl, mask of the PnP stage) and `start` (the poses
+        handed to the refinement).
+        keep_tracks=True appends the rows to those `tracks()` returns.  The map
+        is not changed, nor what `observe` left for `score` and `spawn`.  One
+        stream, no host synchronisation: after a first call has allocated the
+        buffers it can be captured in a graph (host arrays for last_range or
+        prior are uploaded at every call; pass device tensors then).  The map's
+        capacity is bounded by slam_match_unique's t_cap (65535)."""
+        B = int(kp.shape[0])
+        if tuple(kp.shape) != (B, self.kp_cap, 5) or tuple(desc.shape) != (B, self.kp_cap, 32):
+            raise ValueError("LandmarkMap.relocalize: kp / desc do not match (B, kp_cap)")
+        if self.cap > 65535:
+            raise ValueError(f"LandmarkMap.relocalize: capacity {self.cap} > 65535 (slam_match_unique)")
+        K = self._P_host[:, :3]
+        if not np.all(np.isfinite(self._P_host)) or np.any(np.tril(K, -1) != 0.0) or \
+                np.any(np.diag(K) == 0.0):
+            raise ValueError("LandmarkMap.relocalize: P[:, :3] must be upper triangular with a "
+                             "non-zero diagonal (PnP runs with K = P[:, :3])")
+        prm = dict(geometry.PNP_DEFAULTS, **(pnp or {}))
+        b = self._reloc_buffers(B, int(prm["n_hyp"]))
+        if prior is not None:
+            prior = to_dev(prior, torch.float64)
+            if tuple(prior.shape) != (B, 4, 4):
+                raise ValueError("LandmarkMap.relocalize: prior must be [B,4,4]")
+        with torch.cuda.stream(stream):
+            if isinstance(last_range, torch.Tensor) and last_range.is_cuda:
+                rng = last_range
+                if rng.dtype != torch.int32 or tuple(rng.shape) != (B, 2):
+                    raise ValueError("LandmarkMap.relocalize: a device last_range must be int32 [B,2]")
+            else:
+                rng = b["range"]
+                if last_range is None:
+                    last_range = (-(1 << 31), (1 << 31) - 1)
+                lr = np.asarray(last_range)
+                if lr.shape == (2,):
+                    rng[:, 0].fill_(int(lr[0]))
+                    rng[:, 1].fill_(int(lr[1]))
+                elif lr.shape == (B, 2):
+                    rng.copy_(torch.from_numpy(np.ascontiguousarray(lr, np.int32)))
+                else:
+                    raise ValueError("LandmarkMap.relocalize: last_range is None, (lo, hi) or [B,2]")
+            idx2, dist2, good0 = matcher.map_knn2_batch(
+                desc, n_kp, self.desc, self.X, self.last, self.n_dev, rng, max_dist=max_dist,
+                ratio=ratio, ws=b["ws"], out=(b["idx2"], b["dist2"], b["good0"]))
+            owner, _ = matcher.unique_matches(idx2, dist2, good0, n_kp, self.cap,
+                                              out=(b["owner"], b["good"]))
+            # fresh outputs per call: the caller keeps them while later frames run
+            rows = torch.zeros((B, self.rows_cap, 4), dtype=torch.float64, device=self.dev)
+            count = torch.zeros((B,), dtype=torch.int32, device=self.dev)
+            _lib.call("slam_reloc_rows", ptr(owner), ptr(self.n_dev), self.cap, ptr(kp), self.kp_cap,
+                      ptr(self.X), B, int(frame0), self.rows_cap, ptr(rows), ptr(b["matched"]),
+                      ptr(b["Q"]), ptr(b["q"]), stream_ptr(None))
+            rvec, tvec, pn, _ = geometry.pnp_ransac(
+                b["Q"], b["q"], b["matched"], b["K"], seed=seed, item0=item0, out=b["pnp"], ws=b["pnp_ws"],
+                scratch=b["pnp_scratch"], **prm)
+            _lib.call("slam_reloc_pose", ptr(rvec), ptr(tvec), ptr(pn), ptr(b["matched"]), ptr(self.P),
+                      ptr(prior), B, int(min_inliers), ptr(b["start"]), ptr(count), stream_ptr(None))
+            # n_x = capacity: the rows name landmarks below the device count only
+            po, mask, ninl, status, info, _ = geometry.refine_pose(
+                rows, count, self.X, self.cap, b["start"], self.P, min_inliers=min_inliers,
+                out=b["refine"], **refine_options)
+        self.pnp, self.start, self.matched = b["pnp"], b["start"], b["matched"]
+        if keep_tracks:
+            self._tracks.append((rows, count))
         return po, rows, count, mask, ninl, status, info
 
     def reset_tracks(self):

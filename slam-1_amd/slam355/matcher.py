@@ -5,6 +5,8 @@ Reference call sites: /root/reference/keypoint.py:40-51,
 """
 from __future__ import annotations
 
+import ctypes
+
 import numpy as np
 import torch
 
@@ -116,6 +118,49 @@ def unique_matches(idx2, dist2, good, nq, t_cap, *, out=None, stream=None):
     _lib.call("slam_match_unique", ptr(idx2), ptr(dist2), ptr(good), ptr(nq), q_cap, int(t_cap), B,
               ptr(owner), ptr(good_out), stream_ptr(stream))
     return owner, good_out
+
+
+MAP_KNN_SEGMENT = int(_lib.lib.slam_hamming_map_segment())  # landmarks per workgroup of map_knn2_batch
+
+
+def map_knn2_workspace(B, q_cap, x_cap, dev="cuda"):
+    """The partial top-2 workspace of map_knn2_batch (u8; 8 bytes per item,
+    segment of MAP_KNN_SEGMENT landmarks and query)."""
+    nb = ctypes.c_size_t(0)
+    _lib.call("slam_hamming_map_workspace_bytes", int(B), int(q_cap), int(x_cap), ctypes.byref(nb))
+    return torch.empty(int(nb.value), dtype=torch.uint8, device=dev)
+
+
+def map_knn2_batch(q, nq, desc, X, last, n, rng, *, max_dist=64, ratio=(7, 10), ws=None, out=None,
+                   stream=None):
+    """kNN-2 of keypoints against the live landmarks of one map, no window
+    (slam_hamming_map_knn2).
+
+    q [B,q_cap,32] u8, nq [B] i32; the map shared by the batch: desc [x_cap,32]
+    u8, X [x_cap,3] f64, last [x_cap] i32 and the device count n [1] i32; rng
+    [B,2] i32 (lo, hi) per item.  A landmark is eligible iff it lies below n, is
+    alive (X[i,0] not NaN) and lo <= last[i] < hi.  Returns (idx2, dist2
+    [B,q_cap,2] i32 with full landmark indices, good [B,q_cap] u8): good iff two
+    candidates exist, the best is within max_dist and passes ratio[0]/ratio[1]
+    against the second.  Rows >= nq[b] are left untouched (-1 / 0 when allocated
+    here).  ws: map_knn2_workspace(B, q_cap, x_cap), the caller's for calls that
+    may overlap; without one a buffer is allocated for this call."""
+    B, q_cap, _ = q.shape
+    x_cap = int(desc.shape[0])
+    if out is None:
+        idx2 = torch.full((B, q_cap, 2), -1, dtype=torch.int32, device=q.device)
+        dist2 = torch.full((B, q_cap, 2), -1, dtype=torch.int32, device=q.device)
+        good = torch.zeros((B, q_cap), dtype=torch.uint8, device=q.device)
+    else:
+        idx2, dist2, good = out
+    if ws is None:
+        ws = map_knn2_workspace(B, q_cap, x_cap, q.device)
+        if stream is not None and stream != torch.cuda.current_stream(q.device):
+            ws.record_stream(stream)
+    _lib.call("slam_hamming_map_knn2", ptr(q), ptr(nq), q_cap, ptr(desc), ptr(X), ptr(last), ptr(n),
+              x_cap, ptr(rng), B, int(max_dist), int(ratio[0]), int(ratio[1]), ptr(idx2), ptr(dist2),
+              ptr(good), ptr(ws), ws.numel(), stream_ptr(stream))
+    return idx2, dist2, good
 
 
 def track_rows(idx2, good, nq, kp, frame0, *, out=None, stream=None):

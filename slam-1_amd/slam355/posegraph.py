@@ -277,6 +277,54 @@ def edges_from_ba(problem, pairs, scale="unit", rank_tol=1e-8):
     return np.ascontiguousarray(pr, np.int32), meas, info
 
 
+def edge_from_localization(x_ref, pose_c2w, info, return_map=False):
+    """A weighted PoseGraph edge (ref, current) from a pose localized against the
+    map (LandmarkMap.localize / relocalize): the measurement and information in
+    the world -> camera convention of edges_from_ba.
+
+    pose_c2w [4,4] camera-to-world [R | t]; info [6,6] the information of the
+    perturbation X_cam <- Exp(dw) X_cam + dv in the order (dw, dv), as
+    slam_pose_refine defines it; x_ref [6] the reference pose [r, t], world ->
+    camera, treated as exact (its own uncertainty is the graph's).
+      x_cur    = [log(R^T), -R^T t]
+      S_pose   = M info^-1 M^T,  M = [[J_l^-1(r), 0], [-[t]x, I]] at x_cur
+                 (the left perturbation in the coordinates [r, t])
+      meas     = relative_pose(x_ref, x_cur)
+      information = (G S_pose G^T)^-1,  G = the last six columns of
+                 relative_pose_jacobian(x_ref, x_cur).
+    Batched: B poses [B,4,4], info [B,6,6] and one x_ref per frame [B,6] ->
+    ([B,6], [B,6,6]).  np.linalg.LinAlgError when info is not positive
+    definite.  return_map: also the 6x6 map G M from (dw, dv) to the change of
+    meas."""
+    T = np.asarray(pose_c2w, np.float64)
+    single = T.ndim == 2
+    T = T.reshape(-1, 4, 4)
+    B = len(T)
+    A = np.asarray(info, np.float64).reshape(-1, 6, 6)
+    xr = np.asarray(x_ref, np.float64).reshape(-1, 6)
+    if len(A) != B or len(xr) != B:
+        raise ValueError("edge_from_localization: one info and one x_ref per pose")
+    if not (np.all(np.isfinite(T)) and np.all(np.isfinite(A)) and np.all(np.isfinite(xr))):
+        raise ValueError("edge_from_localization: poses, info and x_ref must be finite")
+    meas, information, maps = np.zeros((B, 6)), np.zeros((B, 6, 6)), np.zeros((B, 6, 6))
+    for b in range(B):
+        Rt = T[b, :3, :3].T
+        x_cur = np.concatenate([_so3_log(Rt), -Rt @ T[b, :3, 3]])
+        S = 0.5 * (A[b] + A[b].T)
+        np.linalg.cholesky(S)  # LinAlgError when not positive definite
+        M = np.eye(6)
+        M[:3, :3] = _so3_jr_inv(-x_cur[:3])
+        M[3:, :3] = -_hat(x_cur[3:])
+        L = relative_pose_jacobian(xr[b], x_cur)[:, 6:] @ M
+        Sz = L @ np.linalg.inv(S) @ L.T
+        Sz = 0.5 * (Sz + Sz.T)
+        np.linalg.cholesky(Sz)
+        W = np.linalg.inv(Sz)
+        meas[b], information[b], maps[b] = relative_pose(xr[b], x_cur), 0.5 * (W + W.T), L
+    out = (meas[0], information[0], maps[0]) if single else (meas, information, maps)
+    return out if return_map else out[:2]
+
+
 CHI2_6_99 = 16.811893829770927  # the 0.99 quantile of chi^2 with 6 degrees of freedom
 
 
