@@ -541,6 +541,107 @@ int slam_rows_remap(const double* d_rows, const int32_t* d_count, int rows_cap, 
                     void* stream);
 
 /* ------------------------------------------------------------------------
+ * Structure-only refinement of the landmarks from their tracks: the poses are
+ * held and every landmark is refined from all of its observations in a window
+ * of frames -- the counterpart of slam_pose_refine, one independent 3x3
+ * problem per landmark.  Asynchronous on `stream`; it allocates nothing and
+ * never synchronises the host.
+ *
+ * Inputs.  d_rows [n_frames][rows_cap][4] f64 and d_count [n_frames] i32
+ * (clamped to [0, rows_cap]) as slam_track_rows and slam_map_spawn write them;
+ * the frame column is not read: the position f in the window names the frame.
+ * d_poses [n_frames][16] f64 row-major camera-to-world (R its 3x3, t its last
+ * column); d_P [12] f64, a 3x4 projection whose fourth column may be non-zero;
+ * d_X [x_cap][3] f64, read and updated in place; *d_n (DEVICE i32, clamped to
+ * [0, x_cap]) the landmark count: landmarks at or beyond it are not touched.
+ *
+ * Observations of landmark i.  For each frame f in ascending order the row
+ * k < count_f whose landmark column equals i exactly; if several rows of a
+ * frame name i, the one with the lowest k, whatever order they are met in (an
+ * integer atomicMin of k, as in slam_map_spawn).  A row whose landmark column
+ * is NaN, negative, >= x_cap or not an integer belongs to nobody.  The rows
+ * need not be sorted.
+ *
+ * Model, for the observation (f, x, y) at the point X, in this order and
+ * without contraction:
+ *   d    = X - t_f
+ *   xc_k = R_f[0][k] d0 + R_f[1][k] d1 + R_f[2][k] d2      (slam_project_landmarks)
+ *   h_i  = P[i][0] xc0 + P[i][1] xc1 + P[i][2] xc2 + P[i][3]
+ *   r    = (h0 (1 / h2) - x, h1 (1 / h2) - y)
+ * VALID AT X iff xc2 > min_depth and h2 > 0.  The 2x3 Jacobian is a R_f^T with
+ * a = ((P[0,:3] - u P[2,:3]) (1 / h2), (P[1,:3] - v P[2,:3]) (1 / h2)):
+ *   J[c][k] = a[c][0] R_f[k][0] + a[c][1] R_f[k][1] + a[c][2] R_f[k][2].
+ * loss 0..3 and loss_scale are those of slam_pose_refine: r and J are scaled
+ * by sqrt(rho'(z)), z = |r|^2 / delta^2, and the term is delta^2 rho(z) (loss 0:
+ * |r|^2).
+ *
+ * Rounds, per landmark.  A landmark whose d_X[i][0] is NaN is dead: status 4,
+ * nothing is written for it.  A_0 = the observations valid at the input point;
+ * fewer than min_obs: status 1.  Each of the n_rounds rounds runs `iters`
+ * Levenberg-Marquardt iterations with lambda starting at 1e-3: H = sum J^T J,
+ * g = sum J^T r and cost = sum term over A IN FRAME ORDER (per observation row
+ * 0 of J, then row 1); the step solves (H + lambda max(diag H, 1e-12)) d = -g
+ * by a 3x3 Cholesky; the trial X + d is accepted iff the factorisation
+ * succeeded, every observation of A is valid at the trial and cost_trial <
+ * cost; lambda <- max(lambda / 10, 1e-12) on accept, min(10 lambda, 1e12) on
+ * reject.  After each round EVERY observation of the landmark is classified:
+ * an inlier iff valid and its unweighted |r|^2 <= gate^2; the inliers are the
+ * next round's A; fewer than min_obs of them: status 2, and the rounds end.
+ *
+ * Guard.  After the last round H is formed over the final inliers at the
+ * final point, robust-weighted and undamped, and factored: with L L^T = H and
+ * M = L^-1, var = max_i sum_k M[k][i]^2, the largest diagonal entry of H^-1, in
+ * m^2 per px^2 of observation variance.  Status 3 iff a pivot is not positive
+ * and finite, or var <= max_var is false; max_var = +inf leaves the pivot test
+ * alone.  Without the guard a landmark near the axis of motion (no parallax)
+ * takes an unconstrained step and is thrown far away: a status-3 landmark
+ * keeps its position.
+ *
+ * Outputs.
+ *   d_X                       rewritten only for status 0; for every other
+ *                             status the input point stays bit for bit
+ *   d_status [x_cap] i32      0 refined; 1 fewer than min_obs observations
+ *                             valid at the input point; 2 the inliers fell
+ *                             below min_obs after a round; 3 the guard; 4 dead;
+ *                             -1 at and beyond *d_n
+ *   d_nobs [x_cap] i32        the final inliers (status 0, 3), -1 otherwise
+ *   d_cost [x_cap] f64        sum of term over the final inliers at the final
+ *                             point (status 0, 3), 0 otherwise
+ *   d_info [x_cap][9] f64     that H, row-major and symmetric bit for bit
+ *                             (status 0, 3), zeros otherwise: the landmark's
+ *                             information matrix
+ *   d_var [x_cap] f64         var (status 0, 3; +inf where the factorisation
+ *                             failed), 0 otherwise
+ *   d_mask [n_frames][rows_cap] u8   1 for a row that is the observation of a
+ *                             landmark i < *d_n alive on entry and in its last
+ *                             classification (status 1: valid at the input
+ *                             point); 0 for every other row below count_f
+ *                             (nobody's, the loser among duplicates, a dead
+ *                             landmark's); entries >= count_f are not written
+ *   d_nkilled [1] i32         with kill != 0 every status-2 landmark dies
+ *                             (NaN in all three of d_X[i]) and their number
+ *                             goes here (zeroed on the stream, then an integer
+ *                             atomic add); with kill == 0 it is not written.
+ * d_ws: slam_points_refine_workspace_bytes(n_frames, x_cap) bytes (an i32 per
+ * frame and landmark), 4-byte aligned, contents irrelevant on entry.  Two
+ * launches: one lane per row races k into the index word [f][i]; one lane per
+ * landmark then runs the rounds in its own registers, in frame order, so the
+ * result is that of a sequential evaluation.
+ * SLAM_ERR_ARG before any GPU call (a null pointer is reported by the
+ * argument's name): n_frames outside 1..64; rows_cap outside 1..65535; x_cap
+ * < 1; n_rounds outside 1..8; iters outside 1..50; min_obs < 2; loss outside
+ * 0..3; loss_scale <= 0 with loss != 0; gate <= 0; min_depth NaN; max_var NaN
+ * or <= 0; ws_bytes smaller than the query says. */
+int slam_points_refine_workspace_bytes(int n_frames, int x_cap, size_t* bytes);
+int slam_points_refine(const double* d_rows, const int32_t* d_count, int rows_cap, int n_frames,
+                       const double* d_poses, const double* d_P, double* d_X, const int32_t* d_n,
+                       int x_cap, int loss, double loss_scale, double gate, double min_depth,
+                       int n_rounds, int iters, int min_obs, double max_var, int kill,
+                       int32_t* d_status, int32_t* d_nobs, double* d_cost, double* d_info,
+                       double* d_var, uint8_t* d_mask, int32_t* d_nkilled, void* d_ws,
+                       size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Relocalization: the pose of a frame in the map WITHOUT a predicted pose --
  * what lost tracking and loop closure need.  The frame's keypoints are matched
  * against the descriptors of all eligible landmarks (no window), every landmark

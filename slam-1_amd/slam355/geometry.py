@@ -156,6 +156,71 @@ def refine_pose(rows, count, X, n_x, poses, P, *, loss="huber", loss_scale=2.447
     return po, mask, ninl, status, info, cost
 
 
+def points_workspace(n_frames, x_cap, dev="cuda"):
+    """The index workspace of slam_points_refine for a window of n_frames (u8 tensor)."""
+    nb = ctypes.c_size_t(0)
+    _lib.call("slam_points_refine_workspace_bytes", int(n_frames), int(x_cap), ctypes.byref(nb))
+    return torch.empty(max(int(nb.value), 4), dtype=torch.uint8, device=dev)
+
+
+def refine_points(rows, count, poses, P, X, n_dev, *, loss="huber", loss_scale=2.4477, gate=2.4477,
+                  min_depth=0.1, n_rounds=3, iters=8, min_obs=3, max_var=0.25, kill=False, out=None,
+                  workspace=None, stream=None):
+    """Structure-only refinement of the landmarks from track rows
+    (slam_points_refine): the poses are held, every landmark is refined from all
+    of its observations in the window, X is updated in place.
+
+    rows [F,rows_cap,4] f64 and count [F] i32 as track_rows / LandmarkMap.observe
+    and spawn leave them (the position in the window names the frame), poses
+    [F,4,4] f64 camera-to-world, P 3x4, X [cap,3] f64, n_dev int32 [1] (device)
+    the landmark count -> (status [cap] i32, nobs [cap] i32, cost [cap] f64, info
+    [cap,3,3] f64, var [cap] f64, mask [F,rows_cap] u8, nkilled [1] i32).  status
+    0 refined, 1 too few valid observations, 2 too few inliers, 3 the guard (a
+    pivot of the information not positive, or its largest variance above max_var
+    m^2 per px^2), 4 dead, -1 beyond the count; only status 0 moves the point.
+    kill=True turns the status-2 landmarks dead (NaN) and counts them in nkilled,
+    which is not written otherwise.  `out`: the seven outputs preallocated;
+    `workspace`: points_workspace(F, cap).  With both given the call allocates
+    nothing and can be captured in a graph."""
+    F, rows_cap = int(rows.shape[0]), int(rows.shape[1])
+    dev = rows.device
+    if loss not in REFINE_LOSSES:
+        raise ValueError(f"refine_points: loss {loss!r} is not one of {sorted(REFINE_LOSSES)}")
+    if tuple(rows.shape) != (F, rows_cap, 4) or tuple(poses.shape) != (F, 4, 4) or \
+            tuple(count.shape) != (F,):
+        raise ValueError("refine_points: rows [F,cap,4], count [F] and poses [F,4,4] do not agree")
+    if X.dim() != 2 or int(X.shape[1]) != 3 or not X.is_contiguous() or X.dtype != torch.float64:
+        raise ValueError("refine_points: X must be a contiguous [cap,3] f64 tensor")
+    if rows.dtype != torch.float64 or poses.dtype != torch.float64 or count.dtype != torch.int32 or \
+            n_dev.dtype != torch.int32 or n_dev.numel() != 1:
+        raise ValueError("refine_points: rows, poses f64; count, n_dev (one element) i32")
+    if not (rows.is_contiguous() and poses.is_contiguous() and count.is_contiguous()):
+        raise ValueError("refine_points: rows, count and poses must be contiguous")
+    cap = int(X.shape[0])
+    Pd = P if isinstance(P, torch.Tensor) else torch.as_tensor(np.asarray(P, np.float64),
+                                                               device=dev)
+    if out is None:
+        out = (torch.zeros((cap,), dtype=torch.int32, device=dev),
+               torch.zeros((cap,), dtype=torch.int32, device=dev),
+               torch.zeros((cap,), dtype=torch.float64, device=dev),
+               torch.zeros((cap, 3, 3), dtype=torch.float64, device=dev),
+               torch.zeros((cap,), dtype=torch.float64, device=dev),
+               torch.zeros((F, rows_cap), dtype=torch.uint8, device=dev),
+               torch.zeros((1,), dtype=torch.int32, device=dev))
+    status, nobs, cost, info, var, mask, nkilled = out
+    if tuple(status.shape) != (cap,) or tuple(nobs.shape) != (cap,) or tuple(cost.shape) != (cap,) or \
+            tuple(info.shape) != (cap, 3, 3) or tuple(var.shape) != (cap,) or \
+            tuple(mask.shape) != (F, rows_cap) or nkilled.numel() != 1:
+        raise ValueError("refine_points: out does not match (cap, F, rows_cap)")
+    ws = workspace if workspace is not None else points_workspace(F, cap, dev)
+    _lib.call("slam_points_refine", ptr(rows), ptr(count), rows_cap, F, ptr(poses), ptr(Pd), ptr(X),
+              ptr(n_dev), cap, REFINE_LOSSES[loss], float(loss_scale), float(gate), float(min_depth),
+              int(n_rounds), int(iters), int(min_obs), float(max_var), int(bool(kill)), ptr(status),
+              ptr(nobs), ptr(cost), ptr(info), ptr(var), ptr(mask), ptr(nkilled), ptr(ws),
+              ws.numel(), stream_ptr(stream))
+    return status, nobs, cost, info, var, mask, nkilled
+
+
 def triangulate(ptl, ptr_, count, P_l, P_r, out=None, stream=None):
     """ptl/ptr [B,cap,2] f64, P 3x4 (shared) or [B,3,4] -> X [B,cap,3] f64."""
     B, cap, _ = ptl.shape

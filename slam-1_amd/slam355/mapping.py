@@ -20,6 +20,9 @@ from the keyframes, cull -- runs a batch of frames without a synchronisation.
 `LandmarkMap.relocalize` needs no predicted pose: a global Hamming search
 against the live landmarks (slam_hamming_map_knn2), PnP-RANSAC and the same
 refinement -- for lost tracking and for the measurement of a loop edge.
+`LandmarkMap.refine_points` is the other half of the alternation `localize`
+begins: with the poses held, every landmark is refined from all of its kept
+observations in a window of frames (slam_points_refine), on the stream.
 """
 from __future__ import annotations
 
@@ -133,6 +136,10 @@ class LandmarkMap:
         self._P_host = np.ascontiguousarray(P, np.float64).reshape(3, 4).copy()
         self.pnp = self.start = self.matched = None   # relocalize: PnP's outputs, start poses, row counts
         self._tracks = []    # (rows, count) of every observe call
+        self._kept_poses = {}  # index into _tracks -> the poses step(refine=...) returned for it
+        self._pbufs = {}     # window shape -> the device buffers of refine_points
+        self.pt_status = self.pt_nobs = self.pt_cost = self.pt_info = self.pt_var = None
+        self.pt_mask = self.pt_nkilled = None
         self.uv = self.z = self.idx2 = self.dist2 = self.good = self.owner = None
         self.first = self.cost = None
 
@@ -398,6 +405,7 @@ class LandmarkMap:
     def reset_tracks(self):
         """Forget the rows kept for `tracks()` (the landmarks stay)."""
         self._tracks = []
+        self._kept_poses = {}
 
     # ------------------------------------------------------------ life cycle
     def _fields(self):
@@ -505,13 +513,22 @@ class LandmarkMap:
         return self.remap
 
     def step(self, frame0, poses, kp, desc, n_kp, Xc, pairs, count, keyframe, z_range=(0.1, 70.0),
-             cull=None, stream=None, **localize_options):
+             cull=None, refine=None, stream=None, **localize_options):
         """One batch of frames through the map: `localize` from the predicted
         poses, `score` its second pass, `spawn` at the refined poses from the
         frames with keyframe != 0 and status 0, `cull` at now = frame0 + B - 1
         (`cull`: a dict of its options).  -> what `localize` returns.  One stream,
         no host synchronisation: after a first call has allocated the buffers it
-        can be captured in a graph."""
+        can be captured in a graph.
+
+        refine: None, or a dict of `window` (the number of step calls to look
+        back, this one included; default 1) and any option of `refine_points`.
+        With a dict the call keeps a copy of the poses it returns beside its track
+        rows and, after the cull, refines the landmarks over the rows and poses of
+        the last `window` calls that were made with `refine` (`refine_points`).
+        The window's tensors change from call to call and the copy is a fresh
+        tensor, so `step` with `refine` is not meant for graph capture;
+        `refine_points` called with fixed tensors is."""
         B = int(poses.shape[0])
         with torch.cuda.stream(stream):
             res = self.localize(frame0, poses, kp, desc, n_kp, stream=stream, **localize_options)
@@ -520,7 +537,87 @@ class LandmarkMap:
             self.spawn(frame0, res[0], Xc, pairs, count, kp, desc, n_kp, flags, z_range=z_range,
                        stream=stream)
             self.cull(frame0 + B - 1, stream=stream, **(cull or {}))
+            if refine is not None:
+                opts = dict(refine)
+                window = int(opts.pop("window", 1))
+                if window < 1:
+                    raise ValueError("LandmarkMap.step: refine['window'] must be >= 1")
+                last = len(self._tracks) - 1
+                self._kept_poses[last] = res[0].clone()
+                held = []
+                while len(held) < window and last - len(held) in self._kept_poses:
+                    held.insert(0, self._kept_poses[last - len(held)])
+                for k in [k for k in self._kept_poses if k <= last - window]:
+                    del self._kept_poses[k]     # no later window reaches them
+                self.refine_points(held, stream=stream, **opts)
         return res
+
+    def _points_buffers(self, shape):
+        b = self._pbufs.get(shape)
+        if b is None:
+            F = sum(shape)
+            f64 = dict(dtype=torch.float64, device=self.dev)
+            i32 = dict(dtype=torch.int32, device=self.dev)
+            b = dict(rows=torch.zeros((F, self.rows_cap, 4), **f64), count=torch.zeros((F,), **i32),
+                     poses=torch.zeros((F, 4, 4), **f64),
+                     out=(torch.zeros((self.cap,), **i32), torch.zeros((self.cap,), **i32),
+                          torch.zeros((self.cap,), **f64), torch.zeros((self.cap, 3, 3), **f64),
+                          torch.zeros((self.cap,), **f64),
+                          torch.zeros((F, self.rows_cap), dtype=torch.uint8, device=self.dev),
+                          torch.zeros((1,), **i32)),
+                     ws=geometry.points_workspace(F, self.cap, self.dev))
+            self._pbufs[shape] = b
+        return b
+
+    def refine_points(self, poses, loss="huber", loss_scale=2.4477, gate=2.4477, min_depth=0.1,
+                      n_rounds=3, iters=8, min_obs=3, max_var=0.25, kill=False, stream=None):
+        """Refine the landmarks from their kept observations with the poses held
+        (geometry.refine_points; structure-only BA, the counterpart of `localize`).
+
+        poses: a list of [B_j,4,4] f64 camera-to-world tensors, each going with one
+        of the LAST len(poses) entries of the kept track tensors (the (rows, count)
+        pairs behind `tracks()`, one per observe / localize / step call), oldest
+        first; at most 64 frames in all.  The rows, counts and poses are
+        concatenated on the stream into buffers held per window shape, X is updated
+        in place for the landmarks that come out with status 0, and the outputs
+        stay as attributes: `pt_status`, `pt_nobs`, `pt_cost`, `pt_info`, `pt_var`
+        [capacity...], `pt_mask` [frames,rows_cap] u8 in the order of the window,
+        `pt_nkilled` [1] i32 (written with kill=True only).  -> pt_status.
+        The kept rows are renumbered by `compact`, so it works after one.  No
+        host synchronisation: after a first call of the same window shape has
+        allocated the buffers, a call with the same tensors can be captured in a
+        graph."""
+        poses = list(poses)
+        if not self._tracks:
+            raise ValueError("LandmarkMap.refine_points: no kept tracks")
+        if not poses or len(poses) > len(self._tracks):
+            raise ValueError(f"LandmarkMap.refine_points: {len(poses)} pose tensors for "
+                             f"{len(self._tracks)} kept track entries")
+        kept = self._tracks[-len(poses):]
+        shape = tuple(int(r.shape[0]) for r, _ in kept)
+        for p, B in zip(poses, shape):
+            if tuple(p.shape) != (B, 4, 4):
+                raise ValueError(f"LandmarkMap.refine_points: poses {tuple(p.shape)} beside kept "
+                                 f"rows of {B} frames")
+        if sum(shape) > 64:
+            raise ValueError(f"LandmarkMap.refine_points: {sum(shape)} frames > 64")
+        if any(int(r.shape[1]) != self.rows_cap for r, _ in kept):
+            raise ValueError("LandmarkMap.refine_points: kept rows of another rows_cap")
+        b = self._points_buffers(shape)
+        with torch.cuda.stream(stream):
+            o = 0
+            for (rows, count), p, B in zip(kept, poses, shape):
+                b["rows"][o:o + B].copy_(rows)
+                b["count"][o:o + B].copy_(count)
+                b["poses"][o:o + B].copy_(to_dev(p, torch.float64))
+                o += B
+            out = geometry.refine_points(
+                b["rows"], b["count"], b["poses"], self.P, self.X, self.n_dev, loss=loss,
+                loss_scale=loss_scale, gate=gate, min_depth=min_depth, n_rounds=n_rounds, iters=iters,
+                min_obs=min_obs, max_var=max_var, kill=kill, out=b["out"], workspace=b["ws"])
+        (self.pt_status, self.pt_nobs, self.pt_cost, self.pt_info, self.pt_var, self.pt_mask,
+         self.pt_nkilled) = out
+        return self.pt_status
 
     def tracks(self, compact=False, drop_dead=True):
         """Synchronises: the rows of every observe call so far, concatenated
