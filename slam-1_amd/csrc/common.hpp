@@ -27,6 +27,11 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
     }                                           \
   } while (0)
 
+// One pointer argument per check, so the message names it: "<fn>: <d_name> is null".
+#define NEED(fn, p) SLAM_REQUIRE((p) != nullptr, fn ": " #p " is null")
+#define NEED_ALIGNED16(fn, p) \
+  SLAM_REQUIRE(((uintptr_t)(p) & 15) == 0, fn ": " #p " must be 16-byte aligned")
+
 #define SLAM_HIP(call)                                                        \
   do {                                                                        \
     hipError_t e_ = (call);                                                   \
@@ -42,6 +47,8 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
 #define SLAM_LAUNCHED(name) SLAM_HIP(hipGetLastError())
 
 constexpr int kWave = 64;  // gfx950 wavefront
+
+constexpr int kMaxLandmarks = 1 << 20;  // x_cap of a device-resident map (20-bit index fields)
 
 // workgroups of bs lanes that cover n
 inline int nblk(int n, int bs) { return (n + bs - 1) / bs; }

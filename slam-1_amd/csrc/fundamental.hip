@@ -21,6 +21,7 @@
 // k_fm_finish: one workgroup per pair merges the kSplit bests by the same rule,
 //   reads the winner from the workspace and writes the inlier mask.
 #include "common.hpp"
+#include "wg_scan.hpp"
 
 #include <cmath>
 
@@ -590,29 +591,16 @@ __global__ __launch_bounds__(kCWG) void k_filter_pairs(const int2* __restrict__ 
                                                        int2* __restrict__ out,
                                                        int32_t* __restrict__ out_count) {
   __shared__ int wave_tot[kCWG / 64];
-  __shared__ int carry;
   const int b = blockIdx.x;
-  const int n = min(max(count[b], 0), cap);
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
+  const int n = clamp_count(count[b], cap);
+  int carry = 0;  // pairs written so far (uniform)
   for (int base = 0; base < n; base += kCWG) {
     const int k = base + threadIdx.x;
     const bool keep = k < n && mask[(size_t)b * cap + k] != 0;
-    const unsigned long long m = __ballot(keep);
-    const int before = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_tot[wid] = __popcll(m);
-    __syncthreads();
-    int off = carry;
-    for (int i = 0; i < wid; ++i) off += wave_tot[i];
-    if (keep) out[(size_t)b * cap + off + before] = pairs[(size_t)b * cap + k];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      int tot = 0;
-      for (int i = 0; i < kCWG / 64; ++i) tot += wave_tot[i];
-      carry += tot;
-    }
-    __syncthreads();
+    int tot;
+    const int slot = carry + wg_rank<kCWG>(keep, wave_tot, tot);
+    carry += tot;
+    if (keep) out[(size_t)b * cap + slot] = pairs[(size_t)b * cap + k];
   }
   if (threadIdx.x == 0) out_count[b] = carry;
 }

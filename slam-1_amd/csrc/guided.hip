@@ -6,7 +6,7 @@
 //   k_project      one lane per (frame, landmark): pinhole projection in f64 in
 //                  the operation order the header states, NaN uv when invalid;
 //   k_kp_grid      one workgroup per frame: keypoints binned into square cells
-//                  (count in LDS, workgroup scan, scatter) -> CSR index;
+//                  (count in LDS, wg_exscan of wg_scan.hpp, scatter) -> CSR index;
 //   k_window_knn2  one 16-lane DPP row per query, four queries per wave and no
 //                  workgroup barrier.  Cells are row-major, so the cells a
 //                  window covers in one cell row are ONE contiguous run of
@@ -17,12 +17,14 @@
 //                  the key dist << 16 | j); four xor-shuffle steps merge the row;
 //   k_unique       one workgroup per frame: atomicMin of d1 << 22 | query into
 //                  the owner array, losers cleared, keys decoded;
-//   k_track_rows   one workgroup per frame: order-preserving compaction.
+//   k_track_rows   one workgroup per frame: order-preserving compaction (the rank of
+//                  wg_scan.hpp written out, its second barrier after the row stores).
 // The result of the search is defined by the window predicate alone (the grid
 // only prunes), and every key is unique, so nothing depends on the order in
 // which candidates, lanes or atomics arrive.
 #include "common.hpp"
 #include "hamming_bits.hpp"
+#include "wg_scan.hpp"
 
 namespace {
 
@@ -71,8 +73,8 @@ __global__ __launch_bounds__(kGridWG) void k_kp_grid(
     int32_t* __restrict__ cell_kp) {
   __shared__ int cnt[kMaxCells];  // counts, then the write cursor of every cell
   __shared__ int wtot[kGridWG / kWave];
-  const int b = blockIdx.x, t = threadIdx.x, lane = t & (kWave - 1), wid = t / kWave;
-  const int n = min(max(nkp_arr[b], 0), kp_cap);
+  const int b = blockIdx.x, t = threadIdx.x;
+  const int n = clamp_count(nkp_arr[b], kp_cap);
   kp += (size_t)b * kp_cap * 5;
   cell_ptr += (size_t)b * (ncell + 1);
   cell_kp += (size_t)b * kp_cap;
@@ -88,23 +90,15 @@ __global__ __launch_bounds__(kGridWG) void k_kp_grid(
   const int c0 = min(t * per, ncell), c1 = min(c0 + per, ncell);
   int sum = 0;
   for (int c = c0; c < c1; ++c) sum += cnt[c];
-  int incl = sum;
-#pragma unroll
-  for (int off = 1; off < kWave; off <<= 1) {
-    const int o = __shfl_up(incl, off, kWave);
-    if (lane >= off) incl += o;
-  }
-  if (lane == kWave - 1) wtot[wid] = incl;
-  __syncthreads();
-  int base = incl - sum;
-  for (int w = 0; w < wid; ++w) base += wtot[w];
+  int total;
+  int base = wg_exscan<kGridWG>(sum, wtot, total);
   for (int c = c0; c < c1; ++c) {
     const int k = cnt[c];
     cnt[c] = base;
     cell_ptr[c] = base;
     base += k;
   }
-  if (t == kGridWG - 1) cell_ptr[ncell] = base;  // the last thread's end is the total
+  if (t == 0) cell_ptr[ncell] = total;
   __syncthreads();
   for (int j = t; j < n; j += kGridWG) {
     const int c = cell_of(kp[5 * (size_t)j], kp[5 * (size_t)j + 1], W, H, inv, gw);
@@ -242,7 +236,7 @@ __global__ __launch_bounds__(kItemWG) void k_track_rows(
     int frame0, int rows_cap, double* __restrict__ rows, int32_t* __restrict__ count) {
   __shared__ int wave_tot[kItemWG / kWave];
   const int b = blockIdx.x, t = threadIdx.x, lane = t & (kWave - 1), wid = t / kWave;
-  const int nq = min(max(nq_arr[b], 0), q_cap);
+  const int nq = clamp_count(nq_arr[b], q_cap);
   const size_t qo = (size_t)b * q_cap;
   kp += (size_t)b * kp_cap * 5;
   rows += (size_t)b * rows_cap * 4;

@@ -17,6 +17,7 @@
 //     packed key breaks distance ties by the lower train index (BFMatcher rule).
 #include "common.hpp"
 #include "hamming_bits.hpp"
+#include "wg_scan.hpp"
 
 namespace {
 
@@ -396,13 +397,9 @@ __global__ __launch_bounds__(kCWG) void compact_kernel(
     const int32_t* __restrict__ nq_arr, int q_cap, const double* __restrict__ gate_xyz,
     double gate, int2* __restrict__ pairs, int32_t* __restrict__ count) {
   __shared__ int wave_tot[kCWG / kWave];
-  __shared__ int carry;
   const int item = blockIdx.x;
-  const int nq = min(max(nq_arr[item], 0), q_cap);
-  const int lane = threadIdx.x & (kWave - 1);
-  const int wid = threadIdx.x / kWave;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
+  const int nq = clamp_count(nq_arr[item], q_cap);
+  int carry = 0;  // pairs written so far (uniform)
   for (int base = 0; base < nq; base += kCWG) {
     const int qi = base + threadIdx.x;
     bool keep = false;
@@ -414,23 +411,13 @@ __global__ __launch_bounds__(kCWG) void compact_kernel(
         keep = fabs(X[0]) < gate && fabs(X[1]) < gate && fabs(X[2]) < gate;
       }
     }
-    const unsigned long long m = __ballot(keep);
-    const int before = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_tot[wid] = __popcll(m);
-    __syncthreads();
-    int off = carry;
-    for (int w = 0; w < wid; ++w) off += wave_tot[w];
+    int tot;
+    const int slot = carry + wg_rank<kCWG>(keep, wave_tot, tot);
+    carry += tot;
     if (keep) {
       const size_t o = (size_t)item * q_cap + qi;
-      pairs[(size_t)item * q_cap + off + before] = make_int2(qi, idx2[o].x);
+      pairs[(size_t)item * q_cap + slot] = make_int2(qi, idx2[o].x);
     }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      int tot = 0;
-      for (int w = 0; w < kCWG / kWave; ++w) tot += wave_tot[w];
-      carry += tot;
-    }
-    __syncthreads();
   }
   if (threadIdx.x == 0) count[item] = carry;
 }

@@ -7,8 +7,8 @@
 //                    into the claim word of its keypoint (workgroup-scope
 //                    atomicMin, as k_unique), the winners are counted;
 //   k_spawn_scatter  one workgroup per frame: sums the counts of the frames
-//                    before its own, ranks its winners (ballot + wave totals, as
-//                    k_track_rows) and writes landmark, owner and track row;
+//                    before its own, ranks its winners (wg_rank, wg_scan.hpp)
+//                    and writes landmark, owner and track row;
 //   k_map_cull       one lane per landmark;
 //   k_compact_count / k_compact_scan / k_compact_scatter
 //                    blocks of 1024 landmarks count their live ones, one
@@ -20,44 +20,13 @@
 #include <climits>
 
 #include "common.hpp"
+#include "wg_scan.hpp"
 
 namespace {
 
 constexpr int kScoreWG = 256;
 constexpr int kItemWG = 1024;  // one workgroup per frame / per block of landmarks
 constexpr int kWaves = kItemWG / kWave;
-
-__device__ __forceinline__ int clampi(int v, int hi) { return min(max(v, 0), hi); }
-
-// Exclusive rank of the lanes with `keep` inside the workgroup, and the
-// workgroup's total; wave_tot is kWaves ints of LDS, reusable after the call.
-__device__ __forceinline__ int wg_rank(bool keep, int* wave_tot, int& total) {
-  const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
-  const unsigned long long m = __ballot(keep);
-  if (lane == 0) wave_tot[wid] = __popcll(m);
-  __syncthreads();
-  int off = 0, tot = 0;
-  for (int w = 0; w < kWaves; ++w) {
-    off += w < wid ? wave_tot[w] : 0;
-    tot += wave_tot[w];
-  }
-  __syncthreads();  // wave_tot may be written again
-  total = tot;
-  return off + __popcll(m & ((1ull << lane) - 1ull));
-}
-
-// Sum of v over the workgroup (every lane gets it); red is kWaves ints of LDS.
-__device__ __forceinline__ int wg_sum(int v, int* red) {
-  const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  if (lane == 0) red[wid] = v;
-  __syncthreads();
-  int s = 0;
-  for (int w = 0; w < kWaves; ++w) s += red[w];
-  __syncthreads();
-  return s;
-}
 
 __global__ __launch_bounds__(kScoreWG) void k_map_score(
     const float* __restrict__ uv, const uint8_t* __restrict__ good,
@@ -110,12 +79,12 @@ struct SpawnArgs {
 __global__ __launch_bounds__(kItemWG) void k_spawn_claim(const SpawnArgs a) {
   __shared__ int red[kWaves];
   const int b = blockIdx.x, t = threadIdx.x;
-  if (b == 0 && t == 0) *a.n0 = clampi(*a.n, a.x_cap);
+  if (b == 0 && t == 0) *a.n0 = clamp_count(*a.n, a.x_cap);
   if (!a.spawn[b]) {  // uniform
     if (t == 0) a.total[b] = 0;
     return;
   }
-  const int count = clampi(a.count[b], a.p_cap), nkp = clampi(a.nkp[b], a.kp_cap);
+  const int count = clamp_count(a.count[b], a.p_cap), nkp = clamp_count(a.nkp[b], a.kp_cap);
   const double* Xc = a.Xc + (size_t)b * a.p_cap * 3;
   const int2* pairs = a.pairs + (size_t)b * a.p_cap;
   const int32_t* owner = a.owner + (size_t)b * a.kp_cap;
@@ -139,7 +108,7 @@ __global__ __launch_bounds__(kItemWG) void k_spawn_claim(const SpawnArgs a) {
         __hip_atomic_load(&claim[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == k)
       ++c;
   }
-  c = wg_sum(c, red);
+  c = wg_sum<kItemWG>(c, red);
   if (t == 0) a.total[b] = c;
 }
 
@@ -148,10 +117,10 @@ __global__ __launch_bounds__(kItemWG) void k_spawn_scatter(const SpawnArgs a) {
   const int b = blockIdx.x, t = threadIdx.x;
   // batch <= kItemWG: one frame total per lane; p_cap <= 2^20 keeps the sums below 2^30
   const int mine = t < a.batch ? a.total[t] : 0;
-  const int before = wg_sum(t < b ? mine : 0, red);
+  const int before = wg_sum<kItemWG>(t < b ? mine : 0, red);
   const int n0 = *a.n0;
   if (b == 0) {
-    const int all = wg_sum(mine, red);
+    const int all = wg_sum<kItemWG>(mine, red);
     if (t == 0) {
       *a.n = min(n0 + all, a.x_cap);
       *a.dropped = max(n0 + all - a.x_cap, 0);
@@ -162,7 +131,7 @@ __global__ __launch_bounds__(kItemWG) void k_spawn_scatter(const SpawnArgs a) {
     if (t == 0) a.spawned[b] = 0;
     return;
   }
-  const int count = clampi(a.count[b], a.p_cap), nkp = clampi(a.nkp[b], a.kp_cap);
+  const int count = clamp_count(a.count[b], a.p_cap), nkp = clamp_count(a.nkp[b], a.kp_cap);
   const double* Xc = a.Xc + (size_t)b * a.p_cap * 3;
   const int2* pairs = a.pairs + (size_t)b * a.p_cap;
   const float* kp = a.kp + (size_t)b * a.kp_cap * 5;
@@ -170,7 +139,7 @@ __global__ __launch_bounds__(kItemWG) void k_spawn_scatter(const SpawnArgs a) {
   int32_t* owner = a.owner + (size_t)b * a.kp_cap;
   const int32_t* claim = a.claim + (size_t)b * a.kp_cap;
   double* rows = a.rows + (size_t)b * a.rows_cap * 4;
-  const int rc0 = clampi(a.rows_count[b], a.rows_cap);
+  const int rc0 = clamp_count(a.rows_count[b], a.rows_cap);
   const double* T = a.poses + 16 * (size_t)b;
   int carry = 0;  // candidates of this frame ranked so far (uniform)
   for (int base = 0; base < count; base += kItemWG) {
@@ -179,7 +148,7 @@ __global__ __launch_bounds__(kItemWG) void k_spawn_scatter(const SpawnArgs a) {
     if (k < count) j = pairs[k].x;
     const bool cand = (unsigned)j < (unsigned)nkp && claim[j] == k;
     int tot;
-    const int r = carry + wg_rank(cand, red, tot);
+    const int r = carry + wg_rank<kItemWG>(cand, red, tot);
     carry += tot;
     if (!cand || r >= room) continue;
     const int i = n0 + before + r;  // < x_cap
@@ -216,7 +185,7 @@ __global__ __launch_bounds__(kScoreWG) void k_map_cull(
     int min_visible, int ratio_num, int ratio_den, int age, int min_found,
     int32_t* __restrict__ nculled) {
   const int i = blockIdx.x * kScoreWG + threadIdx.x;
-  if (i >= clampi(*n_ptr, x_cap)) return;
+  if (i >= clamp_count(*n_ptr, x_cap)) return;
   if (X[3 * (size_t)i] != X[3 * (size_t)i]) return;  // dead already
   const long long v = visible[i], f = found[i];
   const bool weak = v >= min_visible && (long long)ratio_den * f < (long long)ratio_num * v;
@@ -240,35 +209,23 @@ __global__ __launch_bounds__(kItemWG) void k_compact_count(const double* __restr
                                                            const int32_t* __restrict__ n_ptr,
                                                            int x_cap, int32_t* __restrict__ remap) {
   __shared__ int red[kWaves];
-  const int n = clampi(*n_ptr, x_cap);
-  const int c = wg_sum(alive(X, blockIdx.x * kItemWG + threadIdx.x, n) ? 1 : 0, red);
+  const int n = clamp_count(*n_ptr, x_cap);
+  const int c = wg_sum<kItemWG>(alive(X, blockIdx.x * kItemWG + threadIdx.x, n) ? 1 : 0, red);
   if (threadIdx.x == 0) remap[(size_t)blockIdx.x * kItemWG] = c;
 }
 
 __global__ __launch_bounds__(kItemWG) void k_compact_scan(int nb, int32_t* __restrict__ remap,
                                                           int32_t* __restrict__ n_out) {
   __shared__ int wtot[kWaves];
-  const int t = threadIdx.x, lane = t & (kWave - 1), wid = t / kWave;
-  int carry = 0;
+  const int t = threadIdx.x;
+  int carry = 0;  // live landmarks of the blocks scanned so far (uniform)
   for (int base = 0; base < nb; base += kItemWG) {
     const int blk = base + t;
     const int c = blk < nb ? remap[(size_t)blk * kItemWG] : 0;
-    int incl = c;
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-      const int o = __shfl_up(incl, off, kWave);
-      if (lane >= off) incl += o;
-    }
-    if (lane == kWave - 1) wtot[wid] = incl;
-    __syncthreads();
-    int off = carry, tot = 0;
-    for (int w = 0; w < kWaves; ++w) {
-      off += w < wid ? wtot[w] : 0;
-      tot += wtot[w];
-    }
-    if (blk < nb) remap[(size_t)blk * kItemWG] = off + incl - c;
+    int tot;
+    const int before = carry + wg_exscan<kItemWG>(c, wtot, tot);
+    if (blk < nb) remap[(size_t)blk * kItemWG] = before;
     carry += tot;
-    __syncthreads();
   }
   if (t == 0) *n_out = carry;
 }
@@ -287,11 +244,11 @@ __global__ __launch_bounds__(kItemWG) void k_compact_scatter(const CompactArgs a
   __shared__ int red[kWaves];
   __shared__ int base_s;
   const int i = blockIdx.x * kItemWG + threadIdx.x;
-  const int n = clampi(*a.n, a.x_cap);
+  const int n = clamp_count(*a.n, a.x_cap);
   if (threadIdx.x == 0) base_s = a.remap[(size_t)blockIdx.x * kItemWG];
   const bool keep = alive(a.X, i, n);
   int tot;
-  const int r = wg_rank(keep, red, tot);  // its barriers publish base_s as well
+  const int r = wg_rank<kItemWG>(keep, red, tot);  // its barriers publish base_s as well
   if (i >= a.x_cap) return;
   const int d = base_s + r;
   a.remap[i] = keep ? d : -1;
@@ -312,7 +269,7 @@ __global__ __launch_bounds__(kItemWG) void k_rows_remap(
     int32_t* __restrict__ count_out) {
   __shared__ int red[kWaves];
   const int b = blockIdx.x, t = threadIdx.x;
-  const int count = clampi(count_arr[b], rows_cap);
+  const int count = clamp_count(count_arr[b], rows_cap);
   rows += (size_t)b * rows_cap * 4;
   rows_out += (size_t)b * rows_cap * 4;
   int carry = 0;
@@ -324,7 +281,7 @@ __global__ __launch_bounds__(kItemWG) void k_rows_remap(
       if (v > -1.0 && v < (double)x_cap) l = remap[(int)v];
     }
     int tot;
-    const int r = carry + wg_rank(l >= 0, red, tot);
+    const int r = carry + wg_rank<kItemWG>(l >= 0, red, tot);
     carry += tot;
     if (l >= 0) {  // r <= k < rows_cap
       double* o = rows_out + 4 * (size_t)r;
@@ -337,17 +294,11 @@ __global__ __launch_bounds__(kItemWG) void k_rows_remap(
   if (t == 0) count_out[b] = carry;
 }
 
-constexpr int kMaxLandmarks = 1 << 20;
-
 size_t spawn_ws_bytes(int batch, int kp_cap) {
   return ((size_t)batch * kp_cap + batch + 1) * sizeof(int32_t);
 }
 
 }  // namespace
-
-#define NEED(fn, p) SLAM_REQUIRE((p) != nullptr, fn ": " #p " is null")
-#define NEED_ALIGNED16(fn, p) \
-  SLAM_REQUIRE(((uintptr_t)(p) & 15) == 0, fn ": " #p " must be 16-byte aligned")
 
 extern "C" int slam_map_score(const float* d_uv, const uint8_t* d_good, const int32_t* d_nq,
                               int x_cap, int batch, int frame0, int32_t* d_visible,

@@ -325,8 +325,6 @@ size_t points_ws_bytes(int n_frames, int x_cap) {
 
 }  // namespace
 
-#define NEED(fn, p) SLAM_REQUIRE((p) != nullptr, fn ": " #p " is null")
-
 extern "C" int slam_points_refine_workspace_bytes(int n_frames, int x_cap, size_t* bytes) {
   SLAM_REQUIRE(n_frames >= 1 && n_frames <= kMaxFrames,
                "slam_points_refine_workspace_bytes: n_frames %d not in 1..%d", n_frames, kMaxFrames);

@@ -29,6 +29,7 @@
 #include "common.hpp"
 #include "hamming_bits.hpp"
 #include "pose_math.hpp"
+#include "wg_scan.hpp"
 
 namespace {
 
@@ -43,10 +44,7 @@ constexpr int kItemWG = 1024;            // k_reloc_rows: one workgroup per fram
 constexpr int kIdxBits = 20;             // partial key = dist << 20 | landmark (< 1 << 20)
 constexpr uint32_t kIdxMask = (1u << kIdxBits) - 1u;
 constexpr uint32_t kNone = 0xFFFFFFFFu;
-constexpr int kMaxLandmarks = 1 << 20;
 static_assert(kSeg >= kWaves && kSeg <= 65536, "the loop's key holds a 16-bit segment-local index");
-
-__device__ __forceinline__ int clampi(int v, int hi) { return min(max(v, 0), hi); }
 
 __global__ __launch_bounds__(kWG) void k_map_knn2_part(
     const uint4* __restrict__ q, const int32_t* __restrict__ nq_arr, int q_cap,
@@ -55,8 +53,8 @@ __global__ __launch_bounds__(kWG) void k_map_knn2_part(
     uint2* __restrict__ part) {
   __shared__ uint32_t lds[kWaves][2][kQPerWG];
   const int tile = blockIdx.x, seg = blockIdx.y, item = blockIdx.z;
-  const int nq = clampi(nq_arr[item], q_cap);
-  const int nt = clampi(*n_ptr, x_cap);
+  const int nq = clamp_count(nq_arr[item], q_cap);
+  const int nt = clamp_count(*n_ptr, x_cap);
   const int q0 = tile * kQPerWG, r0 = seg * kSeg;
   if (q0 >= nq || r0 >= nt) return;  // uniform over the workgroup; the merge reads neither
   const int r1 = min(r0 + kSeg, nt);
@@ -149,8 +147,8 @@ __global__ __launch_bounds__(kMergeWG) void k_map_knn2_merge(
     const int32_t* __restrict__ n_ptr, int x_cap, int nseg, int max_dist, int ratio_num,
     int ratio_den, int2* __restrict__ idx2, int2* __restrict__ dist2, uint8_t* __restrict__ good) {
   const int item = blockIdx.y, qi = blockIdx.x * kMergeWG + threadIdx.x;
-  if (qi >= clampi(nq_arr[item], q_cap)) return;
-  const int live = (clampi(*n_ptr, x_cap) + kSeg - 1) / kSeg;  // the segments that wrote (<= nseg)
+  if (qi >= clamp_count(nq_arr[item], q_cap)) return;
+  const int live = (clamp_count(*n_ptr, x_cap) + kSeg - 1) / kSeg;  // the segments that wrote (<= nseg)
   uint32_t m1 = kNone, m2 = kNone;
   const uint2* p = part + (size_t)item * nseg * q_cap + qi;
   for (int s = 0; s < live; ++s) {
@@ -176,7 +174,7 @@ __global__ __launch_bounds__(kItemWG) void k_reloc_rows(
     double* __restrict__ q) {
   __shared__ int wave_tot[kItemWG / kWave];
   const int b = blockIdx.x, t = threadIdx.x, lane = t & (kWave - 1), wid = t / kWave;
-  const int n = clampi(*n_ptr, x_cap);
+  const int n = clamp_count(*n_ptr, x_cap);
   owner += (size_t)b * x_cap;
   kp += (size_t)b * kp_cap * 5;
   rows += (size_t)b * rows_cap * 4;
@@ -267,10 +265,6 @@ bool knn2_shape_ok(const char* fn, int batch, int q_cap, int x_cap) {
 }
 
 }  // namespace
-
-#define NEED(fn, p) SLAM_REQUIRE((p) != nullptr, fn ": " #p " is null")
-#define NEED_ALIGNED16(fn, p) \
-  SLAM_REQUIRE(((uintptr_t)(p) & 15) == 0, fn ": " #p " must be 16-byte aligned")
 
 extern "C" int slam_hamming_map_segment(void) { return kSeg; }
 

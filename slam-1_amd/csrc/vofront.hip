@@ -30,12 +30,14 @@
 //    the 3x3 median.
 #include "common.hpp"
 #include "dlt.hpp"
+#include "wg_scan.hpp"
 
 #include <cmath>
 
 namespace {
 
 constexpr int kBS = 256;
+constexpr int kCompactWG = 1024;  // the order-preserving compactions: one workgroup per image
 
 // ------------------------------------------------------------------ FAST
 __device__ __forceinline__ int fast_score_t(const uint8_t* c, int st, int t) {
@@ -176,39 +178,18 @@ __global__ __launch_bounds__(kBS) void k_fast_tiles(const uint8_t* __restrict__ 
 }
 
 // concatenate the tiles of each image (row-major tile order)
-__global__ __launch_bounds__(1024) void k_fast_compact(const float* __restrict__ ws_kp,
-                                                       const int32_t* __restrict__ ws_cnt,
-                                                       int n_tiles, int per_tile,
-                                                       float* __restrict__ kp,
-                                                       int32_t* __restrict__ count, int cap) {
-  __shared__ int wsum[16];
-  __shared__ int total;
-  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wid = t >> 6;
-  const int per = (n_tiles + 1023) / 1024;
+__global__ __launch_bounds__(kCompactWG) void k_fast_compact(
+    const float* __restrict__ ws_kp, const int32_t* __restrict__ ws_cnt, int n_tiles, int per_tile,
+    float* __restrict__ kp, int32_t* __restrict__ count, int cap) {
+  __shared__ int wsum[kCompactWG / kWave];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const int per = (n_tiles + kCompactWG - 1) / kCompactWG;
   const int t0 = min(t * per, n_tiles), t1 = min(t0 + per, n_tiles);
   const int32_t* cnt = ws_cnt + (size_t)b * n_tiles;
   int s = 0;
   for (int i = t0; i < t1; ++i) s += cnt[i];
-  // block exclusive scan of s
-  int inc = s;
-  for (int o = 1; o < 64; o <<= 1) {
-    const int v = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += v;
-  }
-  if (lane == 63) wsum[wid] = inc;
-  __syncthreads();
-  if (t == 0) {
-    int a = 0;
-    for (int i = 0; i < 16; ++i) {
-      const int v = wsum[i];
-      wsum[i] = a;
-      a += v;
-    }
-    total = a;
-  }
-  __syncthreads();
-  int off = wsum[wid] + inc - s;
-  const int tot = total;
+  int tot;
+  int off = wg_exscan<kCompactWG>(s, wsum, tot);
   if (t == 0) count[b] = tot > cap ? -tot - 1 : tot;
   if (tot > cap) return;
   for (int i = t0; i < t1; ++i) {
@@ -1088,42 +1069,18 @@ __device__ __forceinline__ void triangulate_f32(float lx, float ly, float rx, fl
   for (int k = 0; k < 3; ++k) X[k] = (float)h[k] / w;
 }
 
-// Order-preserving compaction helper: block of 1024, returns this item's slot
-// (or -1) and advances `base`.
-__device__ int block_compact(bool keep, int* wsum, int& base) {
-  const int t = threadIdx.x, lane = t & 63, wid = t >> 6;
-  const unsigned long long bal = __ballot(keep);
-  const int pre = __popcll(bal & ((1ull << lane) - 1ull));
-  if (lane == 0) wsum[wid] = __popcll(bal);
-  __syncthreads();
-  int off = 0, tot = 0;
-  for (int i = 0; i < 16; ++i) {
-    const int v = wsum[i];
-    off += i < wid ? v : 0;
-    tot += v;
-  }
-  __syncthreads();
-  const int slot = keep ? base + off + pre : -1;
-  base += tot;
-  return slot;
-}
-
 // track_keypoints filters (visual_odometry.py:102-112; keypoint.py:20-32 with lower bounds)
-__global__ __launch_bounds__(1024) void k_lk_filter(const float* __restrict__ p1, int p1_stride,
-                                                    const float* __restrict__ p2,
-                                                    const uint8_t* __restrict__ status,
-                                                    const float* __restrict__ err,
-                                                    const int32_t* __restrict__ npts, int cap,
-                                                    int H, int W, float max_error, int lower,
-                                                    float* __restrict__ tp1,
-                                                    float* __restrict__ tp2,
-                                                    int32_t* __restrict__ idx,
-                                                    int32_t* __restrict__ count) {
-  __shared__ int wsum[16];
+__global__ __launch_bounds__(kCompactWG) void k_lk_filter(
+    const float* __restrict__ p1, int p1_stride, const float* __restrict__ p2,
+    const uint8_t* __restrict__ status, const float* __restrict__ err,
+    const int32_t* __restrict__ npts, int cap, int H, int W, float max_error, int lower,
+    float* __restrict__ tp1, float* __restrict__ tp2, int32_t* __restrict__ idx,
+    int32_t* __restrict__ count) {
+  __shared__ int wsum[kCompactWG / kWave];
   const int b = blockIdx.x;
-  const int n = min(max(npts[b], 0), cap);
-  int base = 0;
-  for (int c = 0; c < n; c += 1024) {
+  const int n = clamp_count(npts[b], cap);
+  int base = 0;  // points kept so far (uniform)
+  for (int c = 0; c < n; c += kCompactWG) {
     const int i = c + threadIdx.x;
     bool keep = false;
     float x2 = 0.f, y2 = 0.f;
@@ -1134,8 +1091,10 @@ __global__ __launch_bounds__(1024) void k_lk_filter(const float* __restrict__ p1
       keep = status[o] && err[o] < max_error && y2 < (float)H && x2 < (float)W;
       if (lower) keep = keep && y2 > 0.f && x2 > 0.f;
     }
-    const int s = block_compact(keep, wsum, base);
-    if (s >= 0) {
+    int tot;
+    const int s = base + wg_rank<kCompactWG>(keep, wsum, tot);
+    base += tot;
+    if (keep) {
       const size_t q = (size_t)b * cap + s;
       tp1[2 * q] = p1[o * p1_stride];
       tp1[2 * q + 1] = p1[o * p1_stride + 1];
@@ -1148,7 +1107,7 @@ __global__ __launch_bounds__(1024) void k_lk_filter(const float* __restrict__ p1
 }
 
 // calculate_right_qs + calc_3d (visual_odometry.py:114-134)
-__global__ __launch_bounds__(1024) void k_vo_right_qs_3d(
+__global__ __launch_bounds__(kCompactWG) void k_vo_right_qs_3d(
     const float* __restrict__ tp1, const float* __restrict__ tp2, const int32_t* __restrict__ cnt,
     int cap, const float* __restrict__ disp, long long disp1_stride, long long disp2_off, int H,
     int W, float min_disp, float max_disp, const double* __restrict__ Pl,
@@ -1156,13 +1115,13 @@ __global__ __launch_bounds__(1024) void k_vo_right_qs_3d(
     float* __restrict__ q2l, float* __restrict__ q2r, float* __restrict__ Q1,
     float* __restrict__ Q2, double* __restrict__ q1l64, double* __restrict__ q2l64,
     double* __restrict__ Q1_64, double* __restrict__ Q2_64, int32_t* __restrict__ count) {
-  __shared__ int wsum[16];
+  __shared__ int wsum[kCompactWG / kWave];
   const int b = blockIdx.x;
-  const int n = min(max(cnt[b], 0), cap);
+  const int n = clamp_count(cnt[b], cap);
   const float* d1 = disp + b * disp1_stride;
   const float* d2 = d1 + disp2_off;
-  int base = 0;
-  for (int c = 0; c < n; c += 1024) {
+  int base = 0;  // points kept so far (uniform)
+  for (int c = 0; c < n; c += kCompactWG) {
     const int i = c + threadIdx.x;
     bool keep = false;
     float ax = 0.f, ay = 0.f, bx = 0.f, by = 0.f, e1 = 0.f, e2 = 0.f;
@@ -1194,8 +1153,10 @@ __global__ __launch_bounds__(1024) void k_vo_right_qs_3d(
       e2 = look(d2, bx, by);
       keep = inb && min_disp < e1 && e1 < max_disp && min_disp < e2 && e2 < max_disp;
     }
-    const int s = block_compact(keep, wsum, base);
-    if (s >= 0) {
+    int tot;
+    const int s = base + wg_rank<kCompactWG>(keep, wsum, tot);
+    base += tot;
+    if (keep) {
       const size_t q = (size_t)b * cap + s;
       const float ar = ax - e1, br = bx - e2;
       q1l[2 * q] = ax;
@@ -1298,8 +1259,8 @@ extern "C" int slam_fast_tiles(const uint8_t* d_img, int batch, int H, int W, in
   k_fast_tiles<<<dim3((g.n_tiles + 3) / 4, batch), kBS, 4 * g.wave_lds, s>>>(d_img, g, ws_kp,
                                                                              ws_cnt);
   SLAM_LAUNCHED("k_fast_tiles");
-  k_fast_compact<<<batch, 1024, 0, s>>>(ws_kp, ws_cnt, g.n_tiles, per_tile, d_kp, d_count,
-                                        kp_cap);
+  k_fast_compact<<<batch, kCompactWG, 0, s>>>(ws_kp, ws_cnt, g.n_tiles, per_tile, d_kp, d_count,
+                                              kp_cap);
   SLAM_LAUNCHED("k_fast_compact");
   return SLAM_OK;
 }
@@ -1427,10 +1388,9 @@ extern "C" int slam_lk_filter(const float* d_p1, int p1_stride, const float* d_p
   if (batch == 0) return SLAM_OK;
   SLAM_REQUIRE(d_p1 && d_p2 && d_status && d_err && d_npts && d_tp1 && d_tp2 && d_count,
                "slam_lk_filter: null pointer");
-  k_lk_filter<<<batch, 1024, 0, slam::as_stream(stream)>>>(d_p1, p1_stride, d_p2, d_status, d_err,
-                                                           d_npts, cap, H, W, max_error,
-                                                           lower_bounds, d_tp1, d_tp2, d_idx,
-                                                           d_count);
+  k_lk_filter<<<batch, kCompactWG, 0, slam::as_stream(stream)>>>(
+      d_p1, p1_stride, d_p2, d_status, d_err, d_npts, cap, H, W, max_error, lower_bounds, d_tp1,
+      d_tp2, d_idx, d_count);
   SLAM_LAUNCHED("k_lk_filter");
   return SLAM_OK;
 }
@@ -1451,7 +1411,7 @@ extern "C" int slam_vo_right_qs_3d(const float* d_tp1, const float* d_tp2, const
   SLAM_REQUIRE(!!d_q1l64 == !!d_q2l64 && !!d_Q1_64 == !!d_Q2_64,
                "slam_vo_right_qs_3d: f64 outputs come in pairs");
   hipStream_t s = slam::as_stream(stream);
-  k_vo_right_qs_3d<<<batch, 1024, 0, s>>>(
+  k_vo_right_qs_3d<<<batch, kCompactWG, 0, s>>>(
       d_tp1, d_tp2, d_cnt, cap, d_disp, disp1_stride, disp2_offset, H, W, min_disp, max_disp, d_Pl,
       d_Pr, d_q1l, d_q1r, d_q2l, d_q2r, d_Q1, d_Q2, d_q1l64, d_q2l64, d_Q1_64, d_Q2_64, d_count);
   SLAM_LAUNCHED("k_vo_right_qs_3d");

@@ -106,10 +106,14 @@ def _pile(rng, n):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("cell", [16, 32])
-def test_kp_grid(cell):
+@pytest.mark.parametrize("cell,size", [pytest.param(16, (W, H), id="16"), pytest.param(32, (W, H), id="32"),
+                                       pytest.param(16, (640, 480), id="16-640x480")])
+def test_kp_grid(cell, size):
+    """160 x 96: 60 or 15 cells, fewer than the workgroup's 1024 lanes; 640 x 480 at
+    cell 16: 1200 cells, two per lane of the scan."""
     from slam355 import matcher
 
+    W, H = size
     rng = np.random.default_rng(5)
     cap = 300
     kp = np.zeros((3, cap, 5), np.float32)

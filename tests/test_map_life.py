@@ -365,16 +365,22 @@ SPAWN_COUNTS = [0, 1, 63, 64, 65, 256, 257, 300, 400, -2]
 
 
 @functools.lru_cache(maxsize=None)
-def _spawn_case():
+def _spawn_case(wide=False):
+    """wide: three frames of 2049, 2100 and 1025 entries (three and two chunks of
+    the 1024-lane workgroup), most of them candidates."""
     rng = np.random.default_rng(67)
-    B, p_cap, kp_cap, x_cap = 67, 300, 350, 1500
-    count = np.array([SPAWN_COUNTS[b % len(SPAWN_COUNTS)] for b in range(B)], np.int32)
+    B, p_cap, kp_cap, x_cap = (3, 2100, 2100, 2200) if wide else (67, 300, 350, 1500)
+    counts = [2049, 2100, 1025] if wide else SPAWN_COUNTS
+    count = np.array([counts[b % len(counts)] for b in range(B)], np.int32)
     flags = (rng.random(B) < 0.7).astype(np.uint8)
-    flags[:len(SPAWN_COUNTS)] = 1
-    flags[[12, 13, 40]] = 0
-    flags[41] = 2                                        # any non-zero value is a keyframe
+    flags[:len(counts)] = 1
     nkp = rng.integers(200, kp_cap + 1, B).astype(np.int32)
-    nkp[5], nkp[6], nkp[7] = -1, kp_cap + 9, 0
+    if wide:
+        nkp[:] = kp_cap
+    else:
+        flags[[12, 13, 40]] = 0
+        flags[41] = 2                                    # any non-zero value is a keyframe
+        nkp[5], nkp[6], nkp[7] = -1, kp_cap + 9, 0
     z = rng.uniform(1.0, 60.0, (B, p_cap))
     Xc = np.stack([rng.uniform(-0.6, 0.6, (B, p_cap)) * z, rng.uniform(-0.4, 0.4, (B, p_cap)) * z, z], 2)
     kind = rng.integers(0, 20, (B, p_cap))
@@ -386,6 +392,9 @@ def _spawn_case():
     Xc[kind == 5, 2] = np.nextafter(Z_RANGE[1], 0.0)     # one step inside: included
     pairs = rng.integers(-1, kp_cap + 5, (B, p_cap, 2)).astype(np.int32)
     pairs[:, :, 0] = np.where(rng.random((B, p_cap)) < 0.5, pairs[:, :, 0] % 120, pairs[:, :, 0])
+    if wide:                                             # nine entries in ten name a keypoint of their own
+        own = np.stack([rng.permutation(kp_cap)[:p_cap] for _ in range(B)])
+        pairs[:, :, 0] = np.where(rng.random((B, p_cap)) < 0.9, own, pairs[:, :, 0])
     owner = np.where(rng.random((B, kp_cap)) < 0.3, rng.integers(0, 1000, (B, kp_cap)), -1).astype(np.int32)
     kp = rng.uniform(0, 600, (B, kp_cap, 5)).astype(np.float32)
     desc = rng.integers(0, 256, (B, kp_cap, 32), dtype=np.uint8)
@@ -406,13 +415,16 @@ def _ulp_distance(a, b):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n0", [0, 5, 1490, 1500])
-def test_spawn_against_reference(n0):
+@pytest.mark.parametrize("n0,wide", [pytest.param(0, False, id="0"), pytest.param(5, False, id="5"),
+                                     pytest.param(1490, False, id="1490"),
+                                     pytest.param(1500, False, id="1500"),
+                                     pytest.param(0, True, id="wide")])
+def test_spawn_against_reference(n0, wide):
     import torch
     from slam355 import _lib
     from slam355.device import ptr
 
-    c = _spawn_case()
+    c = _spawn_case(wide)
     B, x_cap = c["B"], c["x_cap"]
     m = ml.copy_map(c["map"])
     m["n"] = n0
