@@ -540,6 +540,80 @@ int slam_rows_remap(const double* d_rows, const int32_t* d_count, int rows_cap, 
                     const int32_t* d_remap, int x_cap, double* d_rows_out, int32_t* d_count_out,
                     void* stream);
 
+/* 5. Fuse.  Spawn makes a landmark from every triangulated keypoint that no
+ *    landmark owns, so a landmark that was in view but failed its match in a
+ *    keyframe gets a twin at the same world point; from then on the twins
+ *    compete for one keypoint in every frame.  Fuse finds such twins in what
+ *    ONE run of steps 1-4 of guided matching left and merges them.
+ *    Inputs: d_uv [batch][x_cap][2] f32 and d_z [batch][x_cap] f64 (the xc2
+ *    slam_project_landmarks writes), d_idx2 [batch][x_cap][2] i32, d_good0
+ *    [batch][x_cap] u8 (step 3's d_good, before the uniqueness pass), d_good
+ *    [batch][x_cap] u8 (step 4's d_good_out), d_owner [batch][kp_cap] i32 (after
+ *    slam_map_spawn or not), d_nq [batch] i32 (clamped to [0, x_cap]; entries at
+ *    or beyond nq_b are stale and not used), and the landmark state with *d_n.
+ *    In frame b, (l, w) is a CANDIDATE PAIR iff
+ *      l < nq_b, good0[b][l] != 0 and good[b][l] == 0 (l passed the descriptor
+ *        tests and lost the keypoint),
+ *      0 <= j = idx2[b][l][0] < kp_cap, 0 <= w = owner[b][j] < nq_b, w != l,
+ *      l and w are below *d_n and alive,
+ *      uv[b][l] and uv[b][w] are finite and du du + dv dv <= px px, du and dv
+ *        the f64 differences of the f32 values (left to right, no contraction),
+ *      |z[b][l] - z[b][w]| <= rel_depth min(z[b][l], z[b][w]) (false with a NaN),
+ *      the Hamming distance of desc[l] and desc[w] is <= max_dist.
+ *    RANK: a outranks b iff found[a] > found[b], or they are equal and a < b;
+ *    found is read as on entry and a negative value counts as 0.  PARENT[i] is
+ *    the best-ranked landmark among i itself and every partner of i in any
+ *    candidate pair of any frame, whichever side i was on; a parent strictly
+ *    outranks its child, so there is no cycle.  This is the forest of best
+ *    partners, NOT connected components: with pairs a-b and b-c where a
+ *    outranks c and c outranks b, b goes to a and c stays; a later call
+ *    catches c.  root(i) follows parent to its fixed point.
+ *    d_to [x_cap] i32 = root(i) for i < *d_n and i for every other index;
+ *    landmark i is FUSED iff to[i] != i.  For every fused i with r = to[i]:
+ *      visible[r] += visible[i], found[r] += found[i] (the merged found /
+ *        visible ratio lies between the two ratios),
+ *      born[r] = min(born[r], born[i]), last[r] = max(last[r], last[i]),
+ *      all three of d_X[i] become NaN: i is dead exactly as a culled landmark;
+ *    desc[i] and i's own counters are left alone, d_X[r] and desc[r] do not
+ *    change.  *d_nfused i32 = the number fused in this call.
+ *    Three launches.  One lane per landmark writes its own rank key
+ *    (INT32_MAX - max(found, 0)) << 32 | i to a u64 word; one lane per (b, l)
+ *    does one 64-bit atomicMin of the better key of a pair into the word of
+ *    the worse-ranked landmark, so the words do not depend on the order of
+ *    arrival; one lane per landmark walks the low halves to its root and
+ *    merges with integer atomics on the root's counters.
+ *    d_ws: slam_map_fuse_workspace_bytes(x_cap) bytes, 8-byte aligned, contents
+ *    irrelevant on entry.  1 <= batch <= 65535, 1 <= kp_cap <= 65535, px > 0,
+ *    rel_depth >= 0 (NaN refused), 0 <= max_dist <= 256. */
+int slam_map_fuse_workspace_bytes(int x_cap, size_t* bytes);
+int slam_map_fuse(const float* d_uv, const double* d_z, const int32_t* d_idx2,
+                  const uint8_t* d_good0, const uint8_t* d_good, const int32_t* d_owner,
+                  const int32_t* d_nq, int batch, int kp_cap, double* d_X, const uint8_t* d_desc,
+                  int32_t* d_visible, int32_t* d_found, int32_t* d_born, int32_t* d_last,
+                  const int32_t* d_n, int x_cap, double px, double rel_depth, int max_dist,
+                  int32_t* d_to, int32_t* d_nfused, void* d_ws, size_t ws_size, void* stream);
+
+/*    Track rows after a fuse.  d_rows [batch][rows_cap][4] f64 and d_count
+ *    [batch] i32 (clamped to [0, rows_cap]) in the format of slam_track_rows;
+ *    d_to [x_cap] i32 as slam_map_fuse wrote it.  A row whose landmark value v
+ *    is an integer in [0, x_cap) stands for v' = d_to[(int)v]; any other row
+ *    (NaN, negative, >= x_cap, not an integer; also one whose d_to entry is
+ *    not in [0, x_cap)) is copied as it is and competes with nobody.  Among
+ *    the rows of one frame with the same v' exactly one is kept: the row with
+ *    v == v' (the survivor's own observation) of the lowest k if there is one,
+ *    otherwise the row of the lowest k -- an integer atomicMin of
+ *    (v != v' ? 65536 : 0) + k.  The kept rows are written to d_rows_out in
+ *    their order with v' as the landmark, and d_count_out [batch] counts them;
+ *    an output may not be its own input.  Afterwards the rows of a frame are
+ *    no longer in ascending landmark order; slam_points_refine and
+ *    slam_pose_refine do not need that order.
+ *    d_ws: slam_rows_fuse_workspace_bytes(batch, x_cap) bytes, 4-byte aligned,
+ *    contents irrelevant on entry.  1 <= batch, rows_cap <= 65535. */
+int slam_rows_fuse_workspace_bytes(int batch, int x_cap, size_t* bytes);
+int slam_rows_fuse(const double* d_rows, const int32_t* d_count, int rows_cap, int batch,
+                   const int32_t* d_to, int x_cap, double* d_rows_out, int32_t* d_count_out,
+                   void* d_ws, size_t ws_size, void* stream);
+
 /* ------------------------------------------------------------------------
  * Structure-only refinement of the landmarks from their tracks: the poses are
  * held and every landmark is refined from all of its observations in a window

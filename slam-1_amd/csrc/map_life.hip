@@ -14,12 +14,20 @@
 //                    blocks of 1024 landmarks count their live ones, one
 //                    workgroup scans the block counts, the blocks scatter;
 //   k_rows_remap     one workgroup per frame: order-preserving compaction of
-//                    the track rows through the remap table.
+//                    the track rows through the remap table;
+//   k_fuse_init / k_fuse_pairs / k_fuse_apply
+//                    one rank key per landmark, one lane per (frame, landmark)
+//                    that lost its keypoint: a 64-bit atomicMin of the better
+//                    key into the worse landmark's word, then one lane per
+//                    landmark walks the words to its root and merges;
+//   k_rows_fuse      one workgroup per frame: the rows of one merged landmark
+//                    race for its claim word, the winners are compacted.
 // Nothing here waits for another workgroup: what one launch leaves for the
 // next goes through memory and the launch boundary.
 #include <climits>
 
 #include "common.hpp"
+#include "hamming_bits.hpp"
 #include "wg_scan.hpp"
 
 namespace {
@@ -294,9 +302,157 @@ __global__ __launch_bounds__(kItemWG) void k_rows_remap(
   if (t == 0) count_out[b] = carry;
 }
 
+struct FuseArgs {
+  const float* uv;
+  const double* z;
+  const int32_t* idx2;
+  const uint8_t *good0, *good;
+  const int32_t *owner, *nq;
+  double* X;
+  const uint4* desc;
+  int32_t *visible, *found, *born, *last;
+  const int32_t* n;
+  int32_t *to, *nfused;
+  unsigned long long* key;  // workspace: [x_cap] rank key of the best partner so far
+  double px2, rel_depth;
+  int max_dist, kp_cap, x_cap;
+};
+
+// lower key = better rank: more often found, then the lower index
+__device__ __forceinline__ unsigned long long rank_key(const int32_t* found, int i) {
+  return ((unsigned long long)(uint32_t)(INT_MAX - max(found[i], 0)) << 32) | (uint32_t)i;
+}
+
+__global__ __launch_bounds__(kScoreWG) void k_fuse_init(const FuseArgs a) {
+  const int i = blockIdx.x * kScoreWG + threadIdx.x;
+  if (i == 0) *a.nfused = 0;
+  if (i < a.x_cap) a.key[i] = rank_key(a.found, i);
+}
+
+__global__ __launch_bounds__(kScoreWG) void k_fuse_pairs(const FuseArgs a) {
+  const int l = blockIdx.x * kScoreWG + threadIdx.x, b = blockIdx.y;
+  const int n = clamp_count(*a.n, a.x_cap);
+  const int lim = min(clamp_count(a.nq[b], a.x_cap), n);  // l and w lie below nq_b and below *d_n
+  if (l >= lim) return;
+  const size_t o = (size_t)b * a.x_cap;
+  if (!a.good0[o + l] || a.good[o + l]) return;  // passed the descriptor tests, lost the keypoint
+  const int j = a.idx2[2 * (o + l)];
+  if ((unsigned)j >= (unsigned)a.kp_cap) return;
+  const int w = a.owner[(size_t)b * a.kp_cap + j];
+  if ((unsigned)w >= (unsigned)lim || w == l) return;
+  if (a.X[3 * (size_t)l] != a.X[3 * (size_t)l] || a.X[3 * (size_t)w] != a.X[3 * (size_t)w]) return;
+  const float ul = a.uv[2 * (o + l)], vl = a.uv[2 * (o + l) + 1];
+  const float uw = a.uv[2 * (o + w)], vw = a.uv[2 * (o + w) + 1];
+  if (!(isfinite(ul) && isfinite(vl) && isfinite(uw) && isfinite(vw))) return;
+  const double du = (double)ul - (double)uw, dv = (double)vl - (double)vw;
+  if (!(du * du + dv * dv <= a.px2)) return;
+  const double zl = a.z[o + l], zw = a.z[o + w];
+  if (!(fabs(zl - zw) <= a.rel_depth * (zl < zw ? zl : zw))) return;  // NaN on either side: no pair
+  const uint4 l0 = a.desc[2 * (size_t)l], l1 = a.desc[2 * (size_t)l + 1];
+  const uint32_t dl[8] = {l0.x, l0.y, l0.z, l0.w, l1.x, l1.y, l1.z, l1.w};
+  if ((int)hd8(dl, a.desc[2 * (size_t)w], a.desc[2 * (size_t)w + 1]) > a.max_dist) return;
+  const unsigned long long kl = rank_key(a.found, l), kw = rank_key(a.found, w);
+  // kl != kw (the indices differ): the worse of the two learns of the better
+  atomicMin(&a.key[kl < kw ? w : l], kl < kw ? kl : kw);
+}
+
+__global__ __launch_bounds__(kScoreWG) void k_fuse_apply(const FuseArgs a) {
+  const int i = blockIdx.x * kScoreWG + threadIdx.x;
+  if (i >= a.x_cap) return;
+  int r = i;
+  if (i < clamp_count(*a.n, a.x_cap)) {
+    // the keys are read-only here; every hop strictly improves the rank
+    for (int hop = 0; hop < a.x_cap; ++hop) {
+      const int p = (int)(a.key[r] & 0xFFFFFFFFull);
+      if (p == r || (unsigned)p >= (unsigned)a.x_cap) break;
+      r = p;
+    }
+  }
+  a.to[i] = r;
+  if (r == i) return;
+  // only roots receive, and a root is not fused: i's own counters are final
+  atomicAdd(&a.visible[r], a.visible[i]);
+  atomicAdd(&a.found[r], a.found[i]);
+  atomicMin(&a.born[r], a.born[i]);
+  atomicMax(&a.last[r], a.last[i]);
+  const double nan = __builtin_nan("");
+  a.X[3 * (size_t)i] = nan;
+  a.X[3 * (size_t)i + 1] = nan;
+  a.X[3 * (size_t)i + 2] = nan;
+  atomicAdd(a.nfused, 1);  // one add per wave after the compiler's lane count
+}
+
+// The landmark that row k stands for after a fuse, or -1 for a row that is
+// copied as it is; own: the row is the survivor's own observation.
+__device__ __forceinline__ int fused_landmark(const double* rows, int k, const int32_t* to,
+                                              int x_cap, bool& own) {
+  own = false;
+  const double v = rows[4 * (size_t)k + 1];
+  if (!(v >= 0.0 && v < (double)x_cap)) return -1;
+  const int l = (int)v;
+  if ((double)l != v) return -1;
+  const int r = to[l];
+  if ((unsigned)r >= (unsigned)x_cap) return -1;
+  own = r == l;
+  return r;
+}
+
+__global__ __launch_bounds__(kItemWG) void k_rows_fuse(
+    const double* __restrict__ rows, const int32_t* __restrict__ count_arr, int rows_cap,
+    const int32_t* __restrict__ to, int x_cap, int32_t* claim, double* __restrict__ rows_out,
+    int32_t* __restrict__ count_out) {
+  __shared__ int red[kWaves];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const int count = clamp_count(count_arr[b], rows_cap);
+  rows += (size_t)b * rows_cap * 4;
+  rows_out += (size_t)b * rows_cap * 4;
+  claim += (size_t)b * x_cap;
+  bool own;
+  // every row sets the word it will race for: the workspace needs no memset
+  for (int k = t; k < count; k += kItemWG) {
+    const int r = fused_landmark(rows, k, to, x_cap, own);
+    if (r >= 0) __hip_atomic_store(&claim[r], INT_MAX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
+  __syncthreads();
+  // k < 65536: the survivor's own rows come before all others, then the lowest k
+  for (int k = t; k < count; k += kItemWG) {
+    const int r = fused_landmark(rows, k, to, x_cap, own);
+    if (r >= 0)
+      __hip_atomic_fetch_min(&claim[r], (own ? 0 : 65536) + k, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
+  __syncthreads();
+  int carry = 0;
+  for (int base = 0; base < count; base += kItemWG) {
+    const int k = base + t;
+    int r = -1;
+    bool keep = false;
+    if (k < count) {
+      r = fused_landmark(rows, k, to, x_cap, own);
+      keep = r < 0 || __hip_atomic_load(&claim[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) ==
+                          (own ? 0 : 65536) + k;
+    }
+    int tot;
+    const int d = carry + wg_rank<kItemWG>(keep, red, tot);
+    carry += tot;
+    if (keep) {  // d <= k < rows_cap
+      double* o = rows_out + 4 * (size_t)d;
+      o[0] = rows[4 * (size_t)k];
+      o[1] = r >= 0 ? (double)r : rows[4 * (size_t)k + 1];
+      o[2] = rows[4 * (size_t)k + 2];
+      o[3] = rows[4 * (size_t)k + 3];
+    }
+  }
+  if (t == 0) count_out[b] = carry;
+}
+
 size_t spawn_ws_bytes(int batch, int kp_cap) {
   return ((size_t)batch * kp_cap + batch + 1) * sizeof(int32_t);
 }
+
+size_t fuse_ws_bytes(int x_cap) { return (size_t)x_cap * sizeof(unsigned long long); }
+
+size_t rows_fuse_ws_bytes(int batch, int x_cap) { return (size_t)batch * x_cap * sizeof(int32_t); }
 
 }  // namespace
 
@@ -509,5 +665,121 @@ extern "C" int slam_rows_remap(const double* d_rows, const int32_t* d_count, int
   k_rows_remap<<<batch, kItemWG, 0, slam::as_stream(stream)>>>(d_rows, d_count, rows_cap, d_remap,
                                                                x_cap, d_rows_out, d_count_out);
   SLAM_LAUNCHED("k_rows_remap");
+  return SLAM_OK;
+}
+
+extern "C" int slam_map_fuse_workspace_bytes(int x_cap, size_t* bytes) {
+  SLAM_REQUIRE(x_cap >= 1 && x_cap <= kMaxLandmarks,
+               "slam_map_fuse_workspace_bytes: x_cap %d not in 1..%d", x_cap, kMaxLandmarks);
+  NEED("slam_map_fuse_workspace_bytes", bytes);
+  *bytes = fuse_ws_bytes(x_cap);
+  return SLAM_OK;
+}
+
+extern "C" int slam_map_fuse(const float* d_uv, const double* d_z, const int32_t* d_idx2,
+                             const uint8_t* d_good0, const uint8_t* d_good, const int32_t* d_owner,
+                             const int32_t* d_nq, int batch, int kp_cap, double* d_X,
+                             const uint8_t* d_desc, int32_t* d_visible, int32_t* d_found,
+                             int32_t* d_born, int32_t* d_last, const int32_t* d_n, int x_cap,
+                             double px, double rel_depth, int max_dist, int32_t* d_to,
+                             int32_t* d_nfused, void* d_ws, size_t ws_size, void* stream) {
+  SLAM_REQUIRE(batch >= 1 && batch <= 65535, "slam_map_fuse: batch %d not in 1..65535", batch);
+  SLAM_REQUIRE(kp_cap >= 1 && kp_cap <= 65535, "slam_map_fuse: kp_cap %d not in 1..65535", kp_cap);
+  SLAM_REQUIRE(x_cap >= 1 && x_cap <= kMaxLandmarks, "slam_map_fuse: x_cap %d not in 1..%d", x_cap,
+               kMaxLandmarks);
+  SLAM_REQUIRE(px > 0.0, "slam_map_fuse: px %g > 0 does not hold", px);
+  SLAM_REQUIRE(rel_depth >= 0.0, "slam_map_fuse: rel_depth %g >= 0 does not hold", rel_depth);
+  SLAM_REQUIRE(max_dist >= 0 && max_dist <= 256, "slam_map_fuse: max_dist %d not in 0..256", max_dist);
+  NEED("slam_map_fuse", d_uv);
+  NEED("slam_map_fuse", d_z);
+  NEED("slam_map_fuse", d_idx2);
+  NEED("slam_map_fuse", d_good0);
+  NEED("slam_map_fuse", d_good);
+  NEED("slam_map_fuse", d_owner);
+  NEED("slam_map_fuse", d_nq);
+  NEED("slam_map_fuse", d_X);
+  NEED("slam_map_fuse", d_desc);
+  NEED("slam_map_fuse", d_visible);
+  NEED("slam_map_fuse", d_found);
+  NEED("slam_map_fuse", d_born);
+  NEED("slam_map_fuse", d_last);
+  NEED("slam_map_fuse", d_n);
+  NEED("slam_map_fuse", d_to);
+  NEED("slam_map_fuse", d_nfused);
+  NEED("slam_map_fuse", d_ws);
+  NEED_ALIGNED16("slam_map_fuse", d_desc);
+  SLAM_REQUIRE(((uintptr_t)d_ws & 7) == 0, "slam_map_fuse: d_ws must be 8-byte aligned");
+  if (ws_size < fuse_ws_bytes(x_cap)) {
+    slam::set_error("slam_map_fuse: ws_size %zu < %zu", ws_size, fuse_ws_bytes(x_cap));
+    return SLAM_ERR_WORKSPACE;
+  }
+  FuseArgs a;
+  a.uv = d_uv;
+  a.z = d_z;
+  a.idx2 = d_idx2;
+  a.good0 = d_good0;
+  a.good = d_good;
+  a.owner = d_owner;
+  a.nq = d_nq;
+  a.X = d_X;
+  a.desc = reinterpret_cast<const uint4*>(d_desc);
+  a.visible = d_visible;
+  a.found = d_found;
+  a.born = d_born;
+  a.last = d_last;
+  a.n = d_n;
+  a.to = d_to;
+  a.nfused = d_nfused;
+  a.key = static_cast<unsigned long long*>(d_ws);
+  a.px2 = px * px;
+  a.rel_depth = rel_depth;
+  a.max_dist = max_dist;
+  a.kp_cap = kp_cap;
+  a.x_cap = x_cap;
+  const int nb = nblk(x_cap, kScoreWG);
+  hipStream_t s = slam::as_stream(stream);
+  k_fuse_init<<<nb, kScoreWG, 0, s>>>(a);
+  SLAM_LAUNCHED("k_fuse_init");
+  k_fuse_pairs<<<dim3(nb, batch), kScoreWG, 0, s>>>(a);
+  SLAM_LAUNCHED("k_fuse_pairs");
+  k_fuse_apply<<<nb, kScoreWG, 0, s>>>(a);
+  SLAM_LAUNCHED("k_fuse_apply");
+  return SLAM_OK;
+}
+
+extern "C" int slam_rows_fuse_workspace_bytes(int batch, int x_cap, size_t* bytes) {
+  SLAM_REQUIRE(batch >= 1 && batch <= 65535, "slam_rows_fuse_workspace_bytes: batch %d not in 1..65535",
+               batch);
+  SLAM_REQUIRE(x_cap >= 1 && x_cap <= kMaxLandmarks,
+               "slam_rows_fuse_workspace_bytes: x_cap %d not in 1..%d", x_cap, kMaxLandmarks);
+  NEED("slam_rows_fuse_workspace_bytes", bytes);
+  *bytes = rows_fuse_ws_bytes(batch, x_cap);
+  return SLAM_OK;
+}
+
+extern "C" int slam_rows_fuse(const double* d_rows, const int32_t* d_count, int rows_cap, int batch,
+                              const int32_t* d_to, int x_cap, double* d_rows_out,
+                              int32_t* d_count_out, void* d_ws, size_t ws_size, void* stream) {
+  SLAM_REQUIRE(batch >= 1 && batch <= 65535, "slam_rows_fuse: batch %d not in 1..65535", batch);
+  SLAM_REQUIRE(rows_cap >= 1 && rows_cap <= 65535, "slam_rows_fuse: rows_cap %d not in 1..65535",
+               rows_cap);
+  SLAM_REQUIRE(x_cap >= 1 && x_cap <= kMaxLandmarks, "slam_rows_fuse: x_cap %d not in 1..%d", x_cap,
+               kMaxLandmarks);
+  NEED("slam_rows_fuse", d_rows);
+  NEED("slam_rows_fuse", d_count);
+  NEED("slam_rows_fuse", d_to);
+  NEED("slam_rows_fuse", d_rows_out);
+  NEED("slam_rows_fuse", d_count_out);
+  NEED("slam_rows_fuse", d_ws);
+  SLAM_REQUIRE(d_rows_out != d_rows, "slam_rows_fuse: d_rows_out aliases d_rows");
+  SLAM_REQUIRE(d_count_out != d_count, "slam_rows_fuse: d_count_out aliases d_count");
+  SLAM_REQUIRE(((uintptr_t)d_ws & 3) == 0, "slam_rows_fuse: d_ws must be 4-byte aligned");
+  if (ws_size < rows_fuse_ws_bytes(batch, x_cap)) {
+    slam::set_error("slam_rows_fuse: ws_size %zu < %zu", ws_size, rows_fuse_ws_bytes(batch, x_cap));
+    return SLAM_ERR_WORKSPACE;
+  }
+  k_rows_fuse<<<batch, kItemWG, 0, slam::as_stream(stream)>>>(
+      d_rows, d_count, rows_cap, d_to, x_cap, static_cast<int32_t*>(d_ws), d_rows_out, d_count_out);
+  SLAM_LAUNCHED("k_rows_fuse");
   return SLAM_OK;
 }

@@ -128,6 +128,11 @@ SIGNATURES = {
                       c_p],
     "slam_map_compact": [c_p] * 7 + [c_int] + [c_p] * 9,
     "slam_rows_remap": [c_p, c_p, c_int, c_int, c_p, c_int, c_p, c_p, c_p],
+    "slam_map_fuse_workspace_bytes": [c_int, ctypes.POINTER(c_size_t)],
+    "slam_map_fuse": [c_p] * 7 + [c_int, c_int] + [c_p] * 7 + [c_int, c_double, c_double, c_int,
+                                                              c_p, c_p, c_p, c_size_t, c_p],
+    "slam_rows_fuse_workspace_bytes": [c_int, c_int, ctypes.POINTER(c_size_t)],
+    "slam_rows_fuse": [c_p, c_p, c_int, c_int, c_p, c_int, c_p, c_p, c_p, c_size_t, c_p],
     "slam_points_refine_workspace_bytes": [c_int, c_int, ctypes.POINTER(c_size_t)],
     "slam_points_refine": [c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_int, c_int, c_double,
                            c_double, c_double, c_int, c_int, c_int, c_double, c_int, c_p, c_p, c_p,

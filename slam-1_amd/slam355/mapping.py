@@ -17,6 +17,8 @@ on a narrower search at the refined pose.  `score`, `spawn`, `cull` and
 `compact` let the map follow the camera (slam_map_score ... slam_map_compact):
 the landmark count lives on the device, so `step` -- localize, score, spawn
 from the keyframes, cull -- runs a batch of frames without a synchronisation.
+`fuse` merges the duplicates the spawn makes (slam_map_fuse, slam_rows_fuse):
+two landmarks that compete for one keypoint become one with the merged track.
 `LandmarkMap.relocalize` needs no predicted pose: a global Hamming search
 against the live landmarks (slam_hamming_map_knn2), PnP-RANSAC and the same
 refinement -- for lost tracking and for the measurement of a loop edge.
@@ -141,6 +143,9 @@ class LandmarkMap:
         self.pt_status = self.pt_nobs = self.pt_cost = self.pt_info = self.pt_var = None
         self.pt_mask = self.pt_nkilled = None
         self.uv = self.z = self.idx2 = self.dist2 = self.good = self.owner = None
+        self.good0 = None    # the window search's good, before the uniqueness pass (fuse reads it)
+        self._fbufs = {}     # batch size -> the device buffers of fuse
+        self.nfused = self.to = None
         self.first = self.cost = None
 
     def add(self, X, desc, frame=0):
@@ -197,8 +202,8 @@ class LandmarkMap:
                 margin=0.0, min_depth=0.1, stream=None):
         """poses [B,4,4] f64 camera-to-world (predicted), kp [B,kp_cap,5] f32,
         desc [B,kp_cap,32] u8, n_kp [B] i32 -> (rows [B,min(capacity,kp_cap),4]
-        f64, count [B] i32) on the device.  `uv`, `z`, `idx2`, `dist2`, `good`
-        (after the uniqueness pass) and `owner` stay as attributes; they are
+        f64, count [B] i32) on the device.  `uv`, `z`, `idx2`, `dist2`, `good0`
+        (before) and `good` (after the uniqueness pass) and `owner` stay as attributes; they are
         overwritten by the next call of the same batch size."""
         return self._observe(frame0, poses, kp, desc, n_kp, radius, max_dist, ratio, margin,
                              min_depth, stream)
@@ -230,6 +235,7 @@ class LandmarkMap:
                 rows, count = out
             matcher.track_rows(idx2, good, b["nq"], kp, frame0, out=(rows, count))
         self.uv, self.z, self.idx2, self.dist2, self.good, self.owner = uv, z, idx2, dist2, good, owner
+        self.good0 = good0
         self._nq = b["nq"]
         if out is None:
             self._tracks.append((rows, count))
@@ -512,14 +518,83 @@ class LandmarkMap:
             self.n, self._exact = int(self.n_dev.item()), True
         return self.remap
 
+    def _fuse_buffers(self, B):
+        b = self._fbufs.get(B)
+        if b is None:
+            nb = ctypes.c_size_t(0)
+            _lib.call("slam_map_fuse_workspace_bytes", self.cap, ctypes.byref(nb))
+            b = dict(ws=torch.empty(int(nb.value), dtype=torch.uint8, device=self.dev),
+                     to=torch.zeros((self.cap,), dtype=torch.int32, device=self.dev),
+                     nfused=torch.zeros((1,), dtype=torch.int32, device=self.dev), rows_ws={})
+            self._fbufs[B] = b
+        return b
+
+    def _rows_fuse_ws(self, b, B):
+        """The claim words of slam_rows_fuse for kept rows of B frames."""
+        ws = b["rows_ws"].get(B)
+        if ws is None:
+            nr = ctypes.c_size_t(0)
+            _lib.call("slam_rows_fuse_workspace_bytes", B, self.cap, ctypes.byref(nr))
+            ws = torch.empty(int(nr.value), dtype=torch.uint8, device=self.dev)
+            b["rows_ws"][B] = ws
+        return ws
+
+    def fuse(self, px=3.0, rel_depth=0.1, max_dist=64, rewrite_tracks=True, stream=None):
+        """Merge duplicate landmarks (slam_map_fuse): a landmark that passed the
+        descriptor tests of the last `observe` (in `localize`: its second pass)
+        but lost its keypoint to another landmark that projects within `px`
+        pixels of it, at a depth within `rel_depth` of its own and with a
+        descriptor within `max_dist` bits, is its duplicate.  Of the two the one
+        found more often survives (ties: the lower index); it takes the other's
+        visible / found counts and the wider born / last span, keeps its own
+        position and descriptor, and the other dies as a culled landmark does.
+        With rewrite_tracks every kept (rows, count) goes through slam_rows_fuse
+        into fresh tensors, so the survivor carries the merged track (one row
+        per frame; the positions in the list stay).  -> (nfused [1] i32, to
+        [capacity] i32: the survivor of every landmark, itself if not fused),
+        buffers held per capacity and batch size, also kept as `nfused` / `to`.
+
+        What the last observe left (`uv`, `owner`, ...) still speaks of the
+        fused indices as if they were alive: score and spawn before fusing.  A
+        later `compact` squeezes the fused landmarks out with no further work.
+        No host synchronisation; `n` is untouched."""
+        if self.uv is None or self.good0 is None:
+            raise ValueError("LandmarkMap.fuse: no observe call to fuse from")
+        B = int(self.uv.shape[0])
+        b = self._fuse_buffers(B)
+        _lib.call("slam_map_fuse", ptr(self.uv), ptr(self.z), ptr(self.idx2), ptr(self.good0),
+                  ptr(self.good), ptr(self.owner), ptr(self._nq), B, self.kp_cap, ptr(self.X),
+                  ptr(self.desc), ptr(self.visible), ptr(self.found), ptr(self.born), ptr(self.last),
+                  ptr(self.n_dev), self.cap, float(px), float(rel_depth), int(max_dist), ptr(b["to"]),
+                  ptr(b["nfused"]), ptr(b["ws"]), b["ws"].numel(), stream_ptr(stream))
+        if rewrite_tracks:
+            with torch.cuda.stream(stream):
+                kept = []
+                for rows, count in self._tracks:
+                    ws = self._rows_fuse_ws(b, int(rows.shape[0]))
+                    out = (torch.zeros_like(rows), torch.zeros_like(count))
+                    _lib.call("slam_rows_fuse", ptr(rows), ptr(count), int(rows.shape[1]),
+                              int(rows.shape[0]), ptr(b["to"]), self.cap, ptr(out[0]), ptr(out[1]),
+                              ptr(ws), ws.numel(), stream_ptr(stream))
+                    kept.append(out)
+                self._tracks = kept
+        self.nfused, self.to = b["nfused"], b["to"]
+        return self.nfused, self.to
+
     def step(self, frame0, poses, kp, desc, n_kp, Xc, pairs, count, keyframe, z_range=(0.1, 70.0),
-             cull=None, refine=None, stream=None, **localize_options):
+             cull=None, refine=None, fuse=None, stream=None, **localize_options):
         """One batch of frames through the map: `localize` from the predicted
         poses, `score` its second pass, `spawn` at the refined poses from the
         frames with keyframe != 0 and status 0, `cull` at now = frame0 + B - 1
         (`cull`: a dict of its options).  -> what `localize` returns.  One stream,
         no host synchronisation: after a first call has allocated the buffers it
         can be captured in a graph.
+
+        fuse: None, or a dict of `fuse`'s options ({}: its defaults).  With a dict
+        the duplicates are merged after the spawn and before the cull, so the
+        merged counts decide the survivor's fate; the kept track tensors are
+        replaced by fresh ones (rewrite_tracks), which a captured graph would
+        not follow.
 
         refine: None, or a dict of `window` (the number of step calls to look
         back, this one included; default 1) and any option of `refine_points`.
@@ -536,6 +611,8 @@ class LandmarkMap:
             flags = (to_dev(keyframe, torch.uint8).ne(0) & res[5].eq(0)).to(torch.uint8)
             self.spawn(frame0, res[0], Xc, pairs, count, kp, desc, n_kp, flags, z_range=z_range,
                        stream=stream)
+            if fuse is not None:
+                self.fuse(stream=stream, **fuse)
             self.cull(frame0 + B - 1, stream=stream, **(cull or {}))
             if refine is not None:
                 opts = dict(refine)
